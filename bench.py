@@ -3,6 +3,7 @@
 (BASELINE.json: "samples/sec/GPU ResNet-50 bf16 + tokens/sec GPT-3-1.3B fleet DP at 1/2/4/8 MI355X").
 
     python bench.py --gpus N --steps K --warmup W            # N>1: spawns N ranks itself
+    python bench.py --gpus N --steps K --warmup W --full     # + the ResNet-50 half of the metric
     torchrun --nproc-per-node N bench.py --gpus N ...         # or the driver's launcher
 
 With ``--gpus N > 1`` and no ``WORLD_SIZE`` in the environment the script starts N worker
@@ -13,9 +14,16 @@ must equal ``--gpus`` or the script exits non-zero.
 Each step = forward + backward + AdamW update (fp32 master weights) of the full
 24-layer GPT-3 1.3B (hidden 2048, 16 heads, ffn 8192, vocab 50304, seq 2048) in
 bf16 on synthetic token ids; weak scaling (micro-batch per GPU fixed).
-The other half of BASELINE's metric, ResNet-50 bf16 samples/sec (batch 256 per GPU, NHWC,
-Momentum), runs on the same ranks right after the GPT timing and is reported inside the same JSON
-line (``config.resnet50_samples_per_sec``, whole job; ``--no-resnet`` skips it). A single-rank job
+A plain run does only what the headline figure needs: set up, warm up, time ``--steps`` steps,
+write the outputs if ``--dump-outputs DIR`` is given, print the result line.
+``--dump-outputs DIR`` writes what the last timed step handed back as ``DIR/<name>.npy`` (float32):
+``loss.npy``, the step's loss, ``params_sample.npy``, a fixed seeded sample of every parameter
+the step updated, in ``model.parameters()`` order, and ``master_sample.npy``, the optimizer's fp32
+master weights at the same positions. Token ids, images and initial weights are
+seeded, so two runs with the same arguments start from identical inputs.
+``--full`` adds the other half of BASELINE's metric, ResNet-50 bf16 samples/sec (batch 256 per GPU,
+NHWC, Momentum): it runs on the same ranks right after the GPT timing and is reported inside the same
+JSON line (``config.resnet50_samples_per_sec``, whole job; ``--no-resnet`` skips it). A single-rank job
 replays that step as one hipGraph and also times it eagerly (``config.resnet50_eager_samples_per_sec``),
 the mode multi-rank jobs use, so the eager numbers form a like-for-like 1 -> N curve;
 ``--model resnet50`` measures only that config.
@@ -77,9 +85,57 @@ def _args():
                     help="ResNet-50: wrap the model in DataParallel (RCCL reducer) even on one rank — checks the "
                          "graph-captured all-reduce path on a single GPU")
     ap.add_argument("--no-resnet", action="store_true",
-                    help="GPT-3 1.3B run: skip the ResNet-50 half of the headline metric (by default it runs after "
-                         "the GPT timing, same --steps/--warmup, and lands in config.resnet50_*)")
+                    help="GPT-3 1.3B run with --full: skip the ResNet-50 half of the headline metric (under --full it "
+                         "runs after the GPT timing, same --steps/--warmup, and lands in config.resnet50_*)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: after the GPT-3 1.3B timing, the ResNet-50 half of "
+                         "BASELINE's metric on the same ranks (graphed and eager), reported in config.resnet50_*")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned to DIR/<name>.npy (float32): "
+                         "loss.npy, params_sample.npy (a fixed seeded sample of every updated parameter) and "
+                         "master_sample.npy (the fp32 master weights at the same positions)")
     return ap.parse_args()
+
+
+_DUMP_PER_PARAM = 4096   # sampled elements per parameter: GPT-3 1.3B's ~300 tensors come to 3.6 MB per file
+
+
+def _dump_outputs(a, rank, loss, params, opt):
+    """--dump-outputs: the loss the last timed step returned and samples of what it left behind for
+    its caller, rank 0's view: the parameters (params_sample.npy) and, where the optimizer keeps fp32
+    master weights of them, those at the same positions (master_sample.npy: the sharper of the two
+    for comparing builds, a bf16 parameter hides an update below its last bit). The positions come
+    from a fixed seed and depend only on the parameter sizes, so two builds write the same elements.
+    Under pipeline parallelism every rank holds the loss the last stage broadcast."""
+    if not a.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    import torch
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    np.save(os.path.join(a.dump_outputs, "loss.npy"), np.asarray([float(loss.item())], dtype=np.float32))
+    masters = opt.state_dict().get("master_weights") or {}
+    rng = np.random.RandomState(20240)
+    parts, mparts = [], []
+    for p in params:
+        t = p._t.detach().reshape(-1)
+        n = t.numel()
+        idx = None
+        if n > _DUMP_PER_PARAM:
+            idx = torch.from_numpy(np.sort(rng.randint(0, n, _DUMP_PER_PARAM))).to(t.device)
+        parts.append((t if idx is None else t[idx]).float().cpu().numpy())
+        m = masters.get(p.name)
+        if m is not None and m._t.numel() == n:
+            m = m._t.detach().reshape(-1)
+            mparts.append((m if idx is None else m[idx.to(m.device)]).float().cpu().numpy())
+    np.save(os.path.join(a.dump_outputs, "params_sample.npy"),
+            np.concatenate(parts) if parts else np.zeros(0, np.float32))
+    if mparts:
+        np.save(os.path.join(a.dump_outputs, "master_sample.npy"), np.concatenate(mparts))
+
+
+def _runs_resnet_half(a):
+    """whether this run times ResNet-50 after GPT-3 1.3B: only under --full"""
+    return bool(a.full) and a.model == "gpt3-1.3b" and not a.no_resnet
 
 
 def _self_launch(a):
@@ -196,7 +252,8 @@ def main():
                        "optimizer": "AdamW fp32-master", "final_loss": round(float(loss.item()), 4),
                        "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)},
         }
-    if a.model == "gpt3-1.3b" and not a.no_resnet:
+    _dump_outputs(a, rank, loss, tr.inner.parameters(), tr.opt)
+    if _runs_resnet_half(a):
         # the second half of BASELINE's metric: ResNet-50 samples/s on the same ranks
         final_loss = float(loss.item())
         del model, tr, loss, ids, inp, lab, step
@@ -310,6 +367,7 @@ def _bench_bert(a, paddle, dist, world, rank, cap_stream):
         step._stream = cap_stream
     elapsed, loss = _timed(a, step, world, rank, dist)
     value = B * world * a.steps / elapsed
+    _dump_outputs(a, rank, loss, model.parameters(), opt)
     if rank == 0:
         print(json.dumps({
             "metric": "samples/sec BERT-base pretraining bf16 (whole job)", "baseline_metric": BASELINE_METRIC,
@@ -416,6 +474,8 @@ def _bench_resnet(a, paddle, dist, world, rank, emit, cap_stream):
         step._stream = cap_stream
     elapsed, loss = _timed(a, step, world, rank, dist)
     value = B * world * a.steps / elapsed
+    if emit:
+        _dump_outputs(a, rank, loss, model.parameters(), opt)
     res = {
             "metric": "samples/sec ResNet-50 bf16 (whole job)", "baseline_metric": BASELINE_METRIC,
             "value": round(value, 2), "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,

@@ -15,10 +15,10 @@ for s in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $OUT/smoke.log 2>&1; rc=$?
       tail -3 $OUT/smoke.log ;;
     bench_picks)
-      PHA_GEMM_PICK_LOG=1 timeout -k 10 400 python bench.py --steps 10 --warmup 3 > $OUT/bench_picks.log 2>&1; rc=$?
+      PHA_GEMM_PICK_LOG=1 timeout -k 10 400 python bench.py --full --steps 10 --warmup 3 > $OUT/bench_picks.log 2>&1; rc=$?
       grep -E "gemm-pick|metric" $OUT/bench_picks.log | tail -40 ;;
     bench)
-      timeout -k 10 400 python bench.py --steps ${BENCH_STEPS:-10} --warmup ${BENCH_WARMUP:-3} ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; rc=$?
+      timeout -k 10 400 python bench.py --full --steps ${BENCH_STEPS:-10} --warmup ${BENCH_WARMUP:-3} ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; rc=$?
       tail -3 $OUT/bench.log ;;
     bench_ln)
       timeout -k 10 300 python tools/bench_ln.py > $OUT/bench_ln.log 2>&1; rc=$?
@@ -27,6 +27,7 @@ for s in "$@"; do
       timeout -k 10 400 python bench.py --model bert-base --steps 10 --warmup 3 > $OUT/bench_bert.log 2>&1; rc=$?
       tail -3 $OUT/bench_bert.log ;;
     bench_gpt_hipmm)
+      # GPT figure only (the linear layers on gemm8p): a plain run, no ResNet half
       PHA_MATMUL_IMPL=hip timeout -k 10 400 python bench.py --steps 10 --warmup 3 > $OUT/bench_gpt_hipmm.log 2>&1; rc=$?
       tail -3 $OUT/bench_gpt_hipmm.log ;;
     bench_gpt13b)
@@ -78,7 +79,7 @@ for s in "$@"; do
     prof)
       export TMPDIR=/tmp
       rm -rf $OUT/prof
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 2 ${BENCH_ARGS:-} > $OUT/prof.log 2>&1; rc=$?
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 $ROOT/bench.py --full --steps 3 --warmup 2 ${BENCH_ARGS:-} > $OUT/prof.log 2>&1; rc=$?
       tail -3 $OUT/prof.log ;;
     prof_resnet)
       export TMPDIR=/tmp
@@ -100,7 +101,7 @@ for s in "$@"; do
       tail -2 $OUT/tune_gpt.log
       if [ $rc = 0 ]; then PYTORCH_TUNABLEOP_VERBOSE=1 timeout -k 10 600 python bench.py --model bert-base --steps 1 --warmup 1 --gemm-tuning tune --gemm-tuning-file $OUT/gemm_tunableop_gfx950.csv > $OUT/tune_bert.log 2>&1; rc=$?; tail -2 $OUT/tune_bert.log; fi ;;
     bench_tuned)
-      timeout -k 10 400 python bench.py --steps 10 --warmup 3 --gemm-tuning db --gemm-tuning-file $OUT/gemm_tunableop_gfx950.csv > $OUT/bench_tuned.log 2>&1; rc=$?
+      timeout -k 10 400 python bench.py --full --steps 10 --warmup 3 --gemm-tuning db --gemm-tuning-file $OUT/gemm_tunableop_gfx950.csv > $OUT/bench_tuned.log 2>&1; rc=$?
       tail -3 $OUT/bench_tuned.log ;;
     bench_gemm)
       timeout -k 10 600 python tools/bench_gemm.py > $OUT/bench_gemm.log 2>&1; rc=$?
@@ -144,7 +145,7 @@ for s in "$@"; do
     rehearse2)
       # two ranks sharing the one GPU over gloo: the multi-rank DP path of bench.py (GPT + ResNet; the
       # multi-rank ResNet step is timed eagerly)
-      PHA_DIST_BACKEND=gloo timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 2 > $OUT/rehearse2.log 2>&1; rc=$?
+      PHA_DIST_BACKEND=gloo timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 2 --full > $OUT/rehearse2.log 2>&1; rc=$?
       grep -E "metric|capture|Error|error" $OUT/rehearse2.log | cut -c1-300 | tail -6 ;;
     bench_forcedp)
       timeout -k 10 400 python bench.py --model resnet50 --force-dp --steps 5 --warmup 3 > $OUT/bench_forcedp.log 2>&1; rc=$?
