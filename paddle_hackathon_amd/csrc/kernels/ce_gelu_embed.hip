@@ -140,12 +140,9 @@ __device__ __forceinline__ float gelu_grad(float x, bool approx) {
     // 9 VALU + exp2 + rcp (log2(e) folded into the polynomial) instead of ~15 + exp + rcp: the
     // dGELU pass over the GPT MLP's [tokens, 4H] pre-activation is memory-bound only when its VALU
     // work stays well under the HBM time
-    constexpr float k = 0.7978845608028654f, c = 0.044715f;
-    constexpr float c0 = -2.f * k * 1.4426950408889634f, c1 = c0 * c;
+    // (the shared definition: common.h)
     const float x2 = x * x;
-    const float sg = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x2, c1, c0)));
-    const float q = x * __builtin_fmaf(x2, 6.f * k * c, 2.f * k) * (1.f - sg);
-    return __builtin_fmaf(q, sg, sg);
+    return gelu_tanh_grad_sig(x, x2, gelu_tanh_sig(x, x2));
   }
   const float cdf = 0.5f * (1.f + erff(x * 0.7071067811865476f));
   const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);

@@ -110,6 +110,22 @@ template <> struct Vec8<float> {
   }
 };
 
+// ---- tanh-GELU through its sigmoid --------------------------------------------------
+// gelu_tanh(x) = 0.5 x (1 + tanh u) = x s with s = sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3), so
+// gelu_tanh'(x) = s + x s (1 - s) 2u'(x), 2u' = 2k (1 + 3c x^2). One exp2 (log2(e) folded into the
+// polynomial) + one rcp give s; value and derivative are plain VALU work on top of it. The one
+// definition behind the dGELU pass (ce_gelu_embed.hip) and the GEMM epilogues (gemm4p.hip).
+__device__ __forceinline__ float gelu_tanh_sig(float x, float x2) {
+  constexpr float k = 0.7978845608028654f, c = 0.044715f;
+  constexpr float c0 = -2.f * k * 1.4426950408889634f, c1 = c0 * c;
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x2, c1, c0)));
+}
+__device__ __forceinline__ float gelu_tanh_grad_sig(float x, float x2, float sg) {
+  constexpr float k = 0.7978845608028654f, c = 0.044715f;
+  const float q = x * __builtin_fmaf(x2, 6.f * k * c, 2.f * k) * (1.f - sg);
+  return __builtin_fmaf(q, sg, sg);
+}
+
 // ---- wave64 / block reductions ------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -45,6 +45,10 @@ enum : int {
   EPI_BIAS = 1,       // + bias[output column] (fp32)
   EPI_GELU = 2,       // NT only: C = gelu_tanh(acc + bias), and aux = acc (the pre-activation before
                       // the bias, what the HIP dGELU + bias-grad pass reads back)
+  EPI_GELU_DAUX = 4,  // with EPI_GELU + EPI_BIAS: aux = gelu_tanh'(acc + bias) instead (from the sigmoid the
+                      // activation already computes), what EPI_MULAUX of the backward GEMM multiplies by
+  EPI_MULAUX = 8,     // NT only, no bias: C = acc * aux, aux an INPUT shaped and strided like C (the MLP's
+                      // fc2 input gradient times the stored GELU derivative; see the MUL epilogue)
   EPI_NOSTORE = 512,  // measurement only: stores dropped by the buffer bounds check (tools/bench_g4p.py)
   EPI_SKIP = 128,     // measurement only: no epilogue at all (fresh tiles just start at C = 0)
   EPI_STAGGER = 4096, // measurement only: workgroup w starts after (w & 7) * ((epi >> 16) & 255) s_sleep(16)
@@ -147,11 +151,44 @@ typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 // 0.5 x (1 + tanh u), in 5 VALU + 2 transcendental instructions (exp2 with log2(e) folded into the
 // polynomial, one reciprocal) instead of ~10 + 2: the epilogue runs beside the next tile's MFMAs at
 // one wave per SIMD, so its VALU count is its cost
-__device__ __forceinline__ float gelu_t(float x) {
-  constexpr float c0 = -2.f * 0.7978845608028654f * 1.4426950408889634f;
-  constexpr float c1 = c0 * 0.044715f;
-  const float arg = x * __builtin_fmaf(x * x, c1, c0);
-  return x * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(arg) + 1.f);
+__device__ __forceinline__ float gelu_t(float x) { return x * gelu_tanh_sig(x, x * x); }
+
+// ---- MUL epilogue (EPI_MULAUX): counted waits for the aux loads -------------------------------------
+// The aux segment of every output pair is loaded by an inline-asm buffer load (the compiler does not
+// see it, so it places no wait of its own, which would drain the LDS-DMAs too) 2 * W loads ahead of
+// the pair that multiplies by it, into a ring of 2 * W register slots. Per MFMA group g of an
+// epilogue phase, in issue order: the schedule's DMA (groups >= DF), the wait for group g's 2 loads,
+// its 2 stores, then the 2 loads of group g + W (while g + W < 16) into the slots just read. The loads
+// of groups 0..W-1 go out when the tile's output geometry is set (a K-tile or more before), followed
+// by at least PB DMAs before the phase starts.
+// mul_younger: VMEM operations issued after group s's second load and before its wait: for s >= W
+// (loaded at the end of group s - W) the DMAs of groups s-W+1..s, the 2 stores + 2 loads of groups
+// s-W+1..s-1; for s < W the prefetch loads after its own, PB, and groups 0..s likewise.
+constexpr int mul_dmas(int a, int b, int DF) { return b - (a > DF ? a : DF) + 1 > 0 ? b - (a > DF ? a : DF) + 1 : 0; }
+constexpr int mul_loads(int a, int b, int W) { return ((b < 15 - W ? b : 15 - W) - a + 1 > 0) ? 2 * ((b < 15 - W ? b : 15 - W) - a + 1) : 0; }
+constexpr int mul_younger(int s, int W, int PB, int DF) {
+  const int n = s >= W ? 2 * (W - 1) + mul_dmas(s - W + 1, s, DF) + mul_loads(s - W + 1, s - 1, W)
+                       : 2 * (W - 1) + PB + mul_dmas(0, s, DF) + mul_loads(0, s - 1, W);
+  return n > 63 ? 63 : n;
+}
+// (the ring slots of group s are free again only after its store_pairs have read them)
+static_assert(mul_younger(15, 6, 8, 8) == 10 + 6 && mul_younger(0, 6, 8, 8) == 10 + 8 && mul_younger(7, 6, 0, 16) == 10 + 10,
+              "mul_younger");
+// s_waitcnt immediate of vmcnt(n) alone on gfx9 (vmcnt in bits 3:0 and 15:14; expcnt, lgkmcnt at their maxima)
+constexpr int vmcnt_imm(int n) { return (n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8); }
+
+// one 16-bit pair of the output type -> fp32
+template <typename T>
+__device__ __forceinline__ void unpk(unsigned q, float& lo, float& hi) {
+  if constexpr (std::is_same<T, bf16_t>::value) {
+    lo = __builtin_bit_cast(float, q << 16);
+    hi = __builtin_bit_cast(float, q & 0xffff0000u);
+  } else {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const h2 h = __builtin_bit_cast(h2, q);
+    lo = (float)h[0];
+    hi = (float)h[1];
+  }
 }
 
 template <typename T>
@@ -222,8 +259,12 @@ struct Sched {
 // with fewer tiles than CUs); each item writes its fp32 partial tile to its slab of p.ws and
 // pha_gemm4p's reduce kernel sums the slabs in slice order (deterministic) into C (+ bias).
 template <typename T, bool AKO, bool BKO, bool OT, bool BIAS, bool SKIPEPI = false, bool SPLIT = false,
-          bool GELU = false, bool RS = false, bool EARLY = false, int LV = 0, bool CS = false>
+          bool GELU = false, bool RS = false, bool EARLY = false, int LV = 0, bool CS = false, bool DAUX = false,
+          bool MUL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm4p_kernel(Args p) {
+  static_assert(!DAUX || (GELU && BIAS), "the derivative aux is a variant of the bias + GELU epilogue");
+  static_assert(!MUL || !(AKO || BKO || OT || BIAS || SPLIT || GELU || RS || CS || SKIPEPI), "MUL: the plain NT build only");
+  static_assert(!MUL || (lv_lwg(LV) == 0 && !lv_wstag(LV) && !lv_stamp(LV)), "MUL: the wait counts assume these DMA placements");
   __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -409,7 +450,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 4);
     else
       e_base = static_cast<const char*>(p.c) + (size_t)bi * p.sc * 2 + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
-    if constexpr (GELU) e_aux = static_cast<const char*>(p.aux) + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
+    if constexpr (GELU || MUL) e_aux = static_cast<const char*>(p.aux) + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
     // (EPI_NOSTORE, measurement only: zero rows, every store is issued and dropped)
     e_rows = (p.epi & EPI_NOSTORE) ? 0 : Mo - r0 - wrow;
     e_cols = No - c0;
@@ -419,7 +460,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // the output are dropped by the buffer range check; a lane whose 8 columns (multiples of 8,
   // No % 8 == 0) start past the last column gets an offset past any size. Only the lane's
   // column offset is a VGPR; row block and pair go to the scalar base / the immediate offset.
-  auto store_pair = [&](const f32x4& x0, const f32x4& x1, int rb, int cb) {
+  //
+  // MUL: the lane's aux segments in flight, a ring of 2 * MW loads of 16 B (see mul_younger). Load li
+  // (0..31) of a tile belongs to pair li & 1 of MFMA group li >> 1 and reads exactly the 16 B that
+  // store_pair writes for that pair, through the same bounds (rows past the output and column
+  // groups past N read as zero). The compiler sees neither the loads nor their latency: every use
+  // of aw[] goes through aux_step's tied operands first.
+  // MW = 8 (64 VGPRs): half the tile's segments are in flight before its epilogue phase starts and
+  // the other half follow one window behind, about one memory latency exposed per tile; MW = 6 cost
+  // two (2822 vs 2392 us for the plain product at 98304 x 8192 x 2048, profiles/mlp_dgelu_epi/)
+  constexpr int MW = 8;
+  u32x4v aw[MUL ? 2 * MW : 2];
+  auto aux_load = [&](int li) {
+    const int g = li >> 1, rb = g >> 1, cb = (g & 1) * 4 + (li & 1) * 2;
+    const size_t bp = (size_t)(e_aux + (size_t)rb * 16 * ldc2);
+    u32x4v rs;
+    rs[0] = __builtin_amdgcn_readfirstlane((unsigned)bp);
+    rs[1] = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32)) & 0xffffu;
+    rs[2] = (unsigned)__builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
+    rs[3] = 0x00020000u;
+    const unsigned voff = (lcol + cb * 16 < e_cols) ? lane_voff : 0x80000000u;
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3"
+                 : "=v"(aw[MUL ? li % (2 * MW) : 0]) : "v"(voff), "s"(rs), "i"(cb * 32) : "memory");
+  };
+  // group s of an epilogue phase: its two segments have landed (aux_wait, before its store_pairs);
+  // their ring slots then take the loads of group s + MW (aux_next, after its store_pairs read them)
+  auto aux_wait = [&](int s, int PB, int DF) {
+    asm volatile("s_waitcnt %2" : "+v"(aw[MUL ? (2 * s) % (2 * MW) : 0]), "+v"(aw[MUL ? (2 * s + 1) % (2 * MW) : 1])
+                 : "i"(vmcnt_imm(mul_younger(s, MW, PB, DF))) : "memory");
+  };
+  auto aux_next = [&](int s) {
+    if (s + MW < 16) {
+      aux_load(2 * (s + MW));
+      aux_load(2 * (s + MW) + 1);
+    }
+  };
+  auto aux_prefetch = [&]() {   // groups 0..MW-1 of the tile set_epi just selected
+#pragma unroll
+    for (int li = 0; li < 2 * MW; ++li) aux_load(li);
+  };
+  auto store_pair = [&](const f32x4& x0, const f32x4& x1, int rb, int cb, int li = 0) {
     // AGPR -> VGPR reads as asm: as plain C++ uses, the register allocator answered the
     // epilogue's reads by splitting every accumulator's live range into VGPR copies at the tile
     // boundary (60-150 spilled VGPRs); opaque, it keeps them in place (0 spills). The last MFMA
@@ -452,7 +532,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((size_t)bhi << 32) | blo), (short)0, nbytes,
                                                0x00020000);
     };
-    if constexpr (GELU)   // the pre-activation (before the bias) for the backward pass
+    if constexpr (MUL) {
+      // the lane's aux segment back to the accumulator layout: the inverse of pack_swap (the swap is
+      // its own inverse), unpacked to fp32, times the fp32 accumulators
+      const u32x4v w = aw[MUL ? li % (2 * MW) : 0];
+      const auto t0 = __builtin_amdgcn_permlane16_swap(w[0], w[2], false, false);
+      const auto t1 = __builtin_amdgcn_permlane16_swap(w[1], w[3], false, false);
+      float m0[4], m1[4];
+      unpk<T>(t0[0], m0[0], m0[1]);
+      unpk<T>(t1[0], m0[2], m0[3]);
+      unpk<T>(t0[1], m1[0], m1[1]);
+      unpk<T>(t1[1], m1[2], m1[3]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v0[e] *= m0[e];
+        v1[e] *= m1[e];
+      }
+    }
+    if constexpr (GELU && !DAUX)   // the pre-activation (before the bias) for the backward pass
       __builtin_amdgcn_raw_buffer_store_b128(pack_swap(v0, v1), rsrc(e_aux), voff + cb * 32, 0, 2);
     if constexpr (BIAS) {   // bias of the lane's pre-swap columns cb*16 + 4fk .. +3 and (cb+1)*16 + ...
       const unsigned char* bs = smem + BIAS_OFF + e_slot * 1024 + (OT ? wr : wc) * 512 + 16 * fk;
@@ -464,7 +561,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         v1[e] += b1[e];
       }
     }
-    if constexpr (GELU) {
+    if constexpr (DAUX) {
+      // aux = gelu_tanh'(acc + bias) from the activation's own sigmoid (5 more VALU per element, no
+      // second exp / rcp): what the backward GEMM's MUL epilogue multiplies its accumulators by
+      // (packed two by two as they come: 4 live registers of derivatives instead of 8)
+      unsigned qd[4];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        float da[2], db[2];
+#pragma unroll
+        for (int e2 = 0; e2 < 2; ++e2) {
+          const int e = 2 * h + e2;
+          const float a = v0[e], a2 = a * a, sa = gelu_tanh_sig(a, a2);
+          const float b = v1[e], b2 = b * b, sb = gelu_tanh_sig(b, b2);
+          da[e2] = gelu_tanh_grad_sig(a, a2, sa);
+          db[e2] = gelu_tanh_grad_sig(b, b2, sb);
+          v0[e] = a * sa;
+          v1[e] = b * sb;
+        }
+        qd[h] = pk<T>(da[0], da[1]);
+        qd[2 + h] = pk<T>(db[0], db[1]);
+      }
+      const auto s0 = __builtin_amdgcn_permlane16_swap(qd[0], qd[2], false, false);
+      const auto s1 = __builtin_amdgcn_permlane16_swap(qd[1], qd[3], false, false);
+      __builtin_amdgcn_raw_buffer_store_b128(u32x4{s0[0], s1[0], s0[1], s1[1]}, rsrc(e_aux), voff + cb * 32, 0, 2);
+    } else if constexpr (GELU) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         v0[e] = gelu_t(v0[e]);
@@ -555,8 +676,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int q = 0; q < 4; ++q) store_f32(acc[i][jb + q], i, jb + q);
       } else if constexpr (MODE == 2) {
         if constexpr (!OT) {   // pairs (j, j+1) of row block i
-          store_pair(acc[i][jb], acc[i][jb + 1], i, jb);
-          store_pair(acc[i][jb + 2], acc[i][jb + 3], i, jb + 2);
+          // (MUL, plain schedule: no DMA in this phase, the 16 of the last phase B before it)
+          if constexpr (MUL) aux_wait(s, 16, 16);
+          store_pair(acc[i][jb], acc[i][jb + 1], i, jb, 2 * s);
+          store_pair(acc[i][jb + 2], acc[i][jb + 3], i, jb + 2, 2 * s + 1);
+          if constexpr (MUL) aux_next(s);
         } else if ((i & 1) == 0) {   // pairs (i, i+1) of output-row block j
 #pragma unroll
           for (int q = 0; q < 4; ++q) store_pair(acc[i][jb + q], acc[i + 1][jb + q], jb + q, i);
@@ -700,8 +824,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int q = 0; q < 4; ++q) store_f32(acc[i][jb + q], i, jb + q);
       } else if constexpr (MODE == 2) {
         if constexpr (!OT) {
-          store_pair(acc[i][jb], acc[i][jb + 1], i, jb);
-          store_pair(acc[i][jb + 2], acc[i][jb + 3], i, jb + 2);
+          // (MUL: this phase's DMAs one per group from RELG on, the 16 - SNA of the phase B before it)
+          if constexpr (MUL) aux_wait(s, 16 - SNA, RELG);
+          store_pair(acc[i][jb], acc[i][jb + 1], i, jb, 2 * s);
+          store_pair(acc[i][jb + 2], acc[i][jb + 3], i, jb + 2, 2 * s + 1);
+          if constexpr (MUL) aux_next(s);
         } else if ((i & 1) == 0) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) store_pair(acc[i][jb + q], acc[i + 1][jb + q], jb + q, i);
@@ -767,6 +894,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (MUL) {   // (and no aux segments: its waits and multiplies run on zeros)
+#pragma unroll
+    for (int i = 0; i < 2 * MW; ++i) aw[i] = u32x4v{0u, 0u, 0u, 0u};
+  }
 
   int s = 0;   // global K-tile step; buffer s & 1
   if constexpr (EARLY && !SKIPEPI && !RS) {
@@ -776,7 +907,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     using M2 = std::integral_constant<int, 2>;
     // VMEM ops younger than the previous K-tile's DMAs at the A/B boundary: phase A's 12 DMAs, plus
     // an epilogue phase's stores (capped at the counter's 63)
-    constexpr int NSTE = (SPLIT || GELU) ? 64 : 32;
+    // (MUL: its 32 stores and the 32 - 2 MW aux loads issued inside the phase)
+    static_assert(!MUL || (RELG == 8 && SNA == 8), "MUL: one DMA per group from RELG on (mul_younger)");
+    constexpr int NSTE = (SPLIT || GELU) ? 64 : MUL ? 64 - 2 * MW : 32;
     constexpr int VB2 = SNA + NSTE > 63 ? 63 : SNA + NSTE;
     // LATE: the wait sits in phase B after all 16 DMAs of the next-next K-tile (+ the stores)
     constexpr int VL2 = 16 + NSTE > 63 ? 63 : 16 + NSTE;
@@ -814,6 +947,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           }
         }
         set_epi(r);
+        if constexpr (MUL) aux_prefetch();
         phaseE(M0{}, no{}, VW2{}, fa1, fb1, fa0, fb0, buf ^ 1, 0, buf, CSY{}, sel(0, 1));
         stage_end();
         ++s;
@@ -904,10 +1038,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       // GELU builds store twice per pair (64 > the counter's 63): wait to 63, one store retired
       if constexpr (RS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       else if constexpr (SPLIT || GELU) asm volatile("s_waitcnt vmcnt(63)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+      // MUL: the 32 stores + the 32 - 2 MW aux loads issued inside the phase
+      else if constexpr (MUL) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" :: "n"(64 - 2 * MW) : "memory");
       else asm volatile("s_waitcnt vmcnt(32)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       bar();
       set_epi(r);   // the next epilogue phase writes this tile
+      if constexpr (MUL) aux_prefetch();
       stage_begin(buf);
       phase(yes{}, M0{}, STB2{}, fa1, fb1, fa0, fb0, buf ^ 1, 0);
       stage_end();
@@ -938,8 +1075,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       if constexpr (SPLIT) {
         store_f32(acc[i][jb], i, jb);
         store_f32(acc[i][jb + 1], i, jb + 1);
-      } else if constexpr (!OT) store_pair(acc[i][jb], acc[i][jb + 1], i, jb);
-      else if ((i & 1) == 0) {
+      } else if constexpr (!OT) {
+        // (MUL: the same rolling window, nothing else in flight: the prefetched groups have landed)
+        if constexpr (MUL) {
+          if ((jb & 3) == 0) aux_wait(2 * i + (jb >> 2), 0, 16);
+        }
+        store_pair(acc[i][jb], acc[i][jb + 1], i, jb, 4 * i + (jb >> 1));
+        if constexpr (MUL) {
+          if ((jb & 3) == 2) aux_next(2 * i + (jb >> 2));
+        }
+      } else if ((i & 1) == 0) {
         store_pair(acc[i][jb], acc[i + 1][jb], jb, i);
         store_pair(acc[i][jb + 1], acc[i + 1][jb + 1], jb + 1, i);
       }
@@ -1524,7 +1669,7 @@ int launch_e(const Args& a, int ako, int bko, int trans, int grid, hipStream_t s
     }
   }
   if constexpr (!BIAS) {
-    if ((a.epi & EPI_ADEEP) && !(a.epi & EPI_GELU) && !ako && !bko && !trans && a.K >= 256) {
+    if ((a.epi & EPI_ADEEP) && !(a.epi & (EPI_GELU | EPI_MULAUX)) && !ako && !bko && !trans && a.K >= 256) {
       hipLaunchKernelGGL((gemm4a_kernel<T>), dim3(grid), dim3(256), 0, st, a);
       return (int)hipGetLastError();
     }
@@ -1535,6 +1680,22 @@ int launch_e(const Args& a, int ako, int bko, int trans, int grid, hipStream_t s
     else
       hipLaunchKernelGGL((gemm4r_kernel<T, BIAS, false>), dim3(grid), dim3(256), 0, st, a);
     return (int)hipGetLastError();
+  }
+  // (pha_gemm4p_batched has checked: EPI_GELU_DAUX comes with GELU + bias, EPI_MULAUX without bias /
+  // GELU / RSTAGE, both NT and not on the ring)
+  if constexpr (BIAS) {
+    if (a.epi & EPI_GELU_DAUX) {   // the bias + GELU epilogue with the derivative in aux, on its three hosts
+      if (!E && (a.epi & EPI_RSTAGE))
+        hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, true, false, false, true, true, false, 0, false, true>), dim3(grid), dim3(256), 0, st, a);
+      else
+        hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, true, false, false, true, false, E, 0, false, true>), dim3(grid), dim3(256), 0, st, a);
+      return (int)hipGetLastError();
+    }
+  } else {
+    if (a.epi & EPI_MULAUX) {   // C = acc * aux; the early schedule in the plain NT default's PIN + SPREAD variant
+      hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, false, false, false, false, false, E, E ? 40 : 0, false, false, true>), dim3(grid), dim3(256), 0, st, a);
+      return (int)hipGetLastError();
+    }
   }
   if (!E && (a.epi & EPI_RSTAGE) && !ako && !bko && !trans) {
     if (a.epi & EPI_GELU)
@@ -1621,6 +1782,17 @@ PHA_API int pha_gemm4p_batched(int dt, const void* a, const void* b, void* c, lo
   if (((size_t)a | (size_t)b | (size_t)c) & 15) return (int)hipErrorInvalidValue;
   if ((epi & g4p::EPI_BIAS) && !bias) return (int)hipErrorInvalidValue;
   if ((epi & g4p::EPI_GELU) && (!aux || ((size_t)aux & 15) || splits > 1)) return (int)hipErrorInvalidValue;
+  // derivative aux / multiply-by-aux epilogues: NT, one unsplit product, aux shaped like C; the
+  // derivative is a variant of bias + GELU, the multiply excludes bias, GELU and register staging
+  if (epi & (g4p::EPI_GELU_DAUX | g4p::EPI_MULAUX)) {
+    if (a_kouter || b_kouter || trans || splits > 1 || batch != 1 || !aux || ((size_t)aux & 15) ||
+        (epi & (g4p::EPI_COLSUM | g4p::EPI_RING)))
+      return (int)hipErrorInvalidValue;
+    if ((epi & g4p::EPI_GELU_DAUX) && ((epi & g4p::EPI_MULAUX) || !(epi & g4p::EPI_GELU) || !(epi & g4p::EPI_BIAS)))
+      return (int)hipErrorInvalidValue;
+    if ((epi & g4p::EPI_MULAUX) && (epi & (g4p::EPI_GELU | g4p::EPI_BIAS | g4p::EPI_RSTAGE)))
+      return (int)hipErrorInvalidValue;
+  }
   // COLSUM: TN, early schedule, no K-start stagger (the K sub-ranges of the tile rows must tile the
   // item's K-tiles in cursor order), fp32 partials [2 * splits * ceil(M / 256)][N] in aux
   if ((epi & g4p::EPI_COLSUM) && (!aux || ((size_t)aux & 3) || !a_kouter || !b_kouter || trans || batch != 1 ||

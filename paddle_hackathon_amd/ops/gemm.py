@@ -30,6 +30,8 @@ EPI_EARLY = 65536    # gemm4p: early-release schedule (read burst + buffer relea
 EPI_RING = 1 << 22   # gemm4p NT: 4-slot ring of 32-deep stages (gemm4r_kernel; K % 64 == 0, K >= 128)
 EPI_ADEEP = 1 << 23  # gemm4p NT, no bias / GELU: 3 A + 2 B LDS slots (gemm4a_kernel; K >= 256)
 EPI_WSTAG = 1 << 24  # gemm4p NT + EARLY: wave w issues its LDS-DMA after MFMA w of a group
+G4P_GELU_DAUX = 4    # gemm4p NT bias + GELU: aux <- gelu_tanh'(acc + bias) instead of the pre-activation
+G4P_MULAUX = 8       # gemm4p NT: C = acc * aux (aux an input shaped like C)
 G4P_COLSUM = 1 << 27  # gemm4p TN + EARLY: column sums of B (bias gradient) from the MFMA B fragments
 G4P_SPREAD_SHIFT = 28  # gemm4p NT + EARLY, bits 28-29: LDS-DMA placement over 24-28 MFMA groups
 _DT = {torch.bfloat16: 1, torch.float16: 2, torch.float32: 0}
@@ -165,13 +167,17 @@ def _group_m(a_kouter, b_kouter, K, N):
 
 
 def gemm_p(a, b, a_kouter=False, b_kouter=False, bias=None, out=None, trans_out=False, epi_extra=0, grid=0,
-           group_m=0, splits=1, gelu_aux=None, colsum=False):
+           group_m=0, splits=1, gelu_aux=None, colsum=False, gelu_deriv=False, mul_aux=None):
     """C = op(A) @ op(B) (+ bias[output column]) on the persistent epilogue-overlapped kernel
     (csrc/kernels/gemm4p.hip). Layouts: NT (False, False), TN (True, True), and with trans_out
     (True, False) the transposed product C^T [N, M] (``nn_p`` runs x @ W through it).
     splits > 1 (TN only): split-K into fp32 slabs + an in-order reduce (few-tile weight gradients).
     gelu_aux (NT only): C = gelu_tanh(A B^T + bias) and gelu_aux <- A B^T (the pre-activation
-    without the bias, shaped and strided like C) from the same epilogue.
+    without the bias, shaped and strided like C) from the same epilogue. With gelu_deriv (needs a
+    bias) gelu_aux <- gelu_tanh'(A B^T + bias) instead: the factor the backward needs, from the
+    sigmoid the activation already computes.
+    mul_aux (NT only, no bias): C = (A B^T) * mul_aux, elementwise on the fp32 accumulators, mul_aux an
+    input shaped and strided like C (the MLP's fc2 input gradient times the stored GELU derivative).
     colsum (TN only): also the column sums of B over K (a linear layer's bias gradient sum_t dY[t]),
     summed by the main loop from the B fragments it already holds; returns (C, fp32 partials
     [2 * splits * ceil(M / 256) (+ 8 workspace rows), N]) — finish with colsum_rows_finish."""
@@ -196,6 +202,17 @@ def gemm_p(a, b, a_kouter=False, b_kouter=False, bias=None, out=None, trans_out=
         assert (a_kouter, b_kouter, trans_out, splits) == (False, False, False, 1)
         assert gelu_aux.shape == c.shape and gelu_aux.stride() == c.stride() and gelu_aux.dtype == c.dtype
         epi |= EPI_GELU
+        if gelu_deriv:
+            assert bias is not None, "the derivative aux is a variant of the bias + GELU epilogue"
+            epi |= G4P_GELU_DAUX
+    else:
+        assert not gelu_deriv
+    if mul_aux is not None:
+        assert (a_kouter, b_kouter, trans_out, splits) == (False, False, False, 1)
+        assert gelu_aux is None and bias is None and not colsum
+        assert mul_aux.shape == c.shape and mul_aux.stride() == c.stride() and mul_aux.dtype == c.dtype
+        epi |= G4P_MULAUX
+        gelu_aux = mul_aux
     part = None
     if colsum:
         assert (a_kouter, b_kouter, trans_out) == (True, True, False) and gelu_aux is None
@@ -510,17 +527,36 @@ def nn(a, b, **epi):
     return gemm(b, a, True, False, trans_out=True, **epi)
 
 
-def mm_nt_bias_gelu(a, bt, bias):
+def mm_nt_bias_gelu(a, bt, bias, deriv=False):
     """(gelu_tanh(a bt^T + bias), a bt^T) in one own-kernel pass (the MLP's fc1 forward), or None
-    when the own kernel does not take the operands"""
+    when the own kernel does not take the operands. deriv: the second result is
+    gelu_tanh'(a bt^T + bias) instead, the factor ``mm_nt_mul`` multiplies the backward by."""
     M, K = a.shape
     N = bt.shape[0]
     if not (_impl() != "library" and a.is_cuda and bt.dtype == a.dtype and a.dtype in (torch.bfloat16, torch.float16)
             and supported(M, N, K, a, bt) and bias is not None and bias.numel() == N):
         return None
     pre = torch.empty(M, N, dtype=a.dtype, device=a.device)
-    act = gemm_p(a, bt, False, False, bias=bias, gelu_aux=pre)
+    act = gemm_p(a, bt, False, False, bias=bias, gelu_aux=pre, gelu_deriv=deriv)
     return act, pre
+
+
+def mm_nt_mul(a, bt, aux, out=None):
+    """(a [M, K] @ bt [N, K]^T) * aux [M, N] in one own-kernel pass: the product's fp32 accumulators
+    times aux in the epilogue (the MLP's fc2 input gradient times the GELU derivative the forward
+    stored), or None when the own kernel does not take the operands. A planned own product under
+    ``auto`` like the fc1 forward: the multiply has no library counterpart to fall back to."""
+    M, K = a.shape
+    N = bt.shape[0]
+    if not (_impl() != "library" and a.is_cuda and bt.dtype == a.dtype and a.dtype in (torch.bfloat16, torch.float16)
+            and aux.dtype == a.dtype and tuple(aux.shape) == (M, N) and supported(M, N, K, a, bt, aux)):
+        return None
+    if out is None:   # C shares aux's row stride (one set of lane offsets serves the load and the store)
+        out = torch.empty_strided((M, N), aux.stride(), dtype=a.dtype, device=a.device)
+    elif not (out.dtype == a.dtype and tuple(out.shape) == (M, N) and out.stride() == aux.stride()
+              and supported(M, N, K, out)):
+        return None
+    return gemm_p(a, bt, False, False, out=out, mul_aux=aux)
 
 
 def mm_nn(a, b):
