@@ -297,6 +297,40 @@ constexpr int kFwdAhead = PHA_FWD_AHEAD;
 constexpr int BM2 = 256;
 constexpr int NT2 = 512;
 
+// ---- persistent launch form (PHA_FA_PERSIST) -------------------------------------------------
+// One workgroup per CU walks the items w, w + nWG, ... of the list the plain grid enumerates
+// (fa_block with G = 0: (b, h) fastest, heaviest causal block first), and item i + 1's per-block
+// operands are requested while item i runs its last tile, so neither the block's load latency nor
+// its store tail stands alone on the CU.
+__device__ __forceinline__ void fa_item(int id, int BH, int& bh, int& blk) {
+  bh = id % BH;
+  blk = id / BH;
+}
+
+// Two accumulator column groups (4 columns each on the lane, the other 4 on lane ^ 32, which holds
+// the same row) -> 8 consecutive columns per lane for one 16-byte store: lanes 0-31 get columns
+// 0-7 of the 16-column pair, lanes 32-63 columns 8-15 (CDNA guide T21)
+__device__ __forceinline__ u32x4 fa_pair16(u32x2 a, u32x2 b) {
+  const auto s0 = __builtin_amdgcn_permlane32_swap(a[0], b[0], false, false);
+  const auto s1 = __builtin_amdgcn_permlane32_swap(a[1], b[1], false, false);
+  return u32x4{s0[0], s1[0], s0[1], s1[1]};
+}
+
+// A 256-row block of 256-B rows by LDS-DMA into a K-tile-shaped image (chunk ^ (row & 15)): 64
+// 1-KiB pieces, 8 per wave of an 8-wave workgroup; rows past `rows` repeat the last one
+template <typename T>
+__device__ __forceinline__ void fa_block_to_lds(const T* base, long stride, int r0, int rows, unsigned lds, int wid,
+                                                int lane) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int piece = wid * 8 + u;
+    const int row = piece * 4 + (lane >> 4);
+    const int ch = (lane & 15) ^ (row & 15);
+    const unsigned voff = (unsigned)(((long)(min(r0 + row, rows - 1) - r0) * stride + ch * 8) * 2);
+    fa_glds16(voff, base + (long)r0 * stride, __builtin_amdgcn_readfirstlane(lds + piece * 1024));
+  }
+}
+
 // element strides (token, head) of each operand, so packed [B, S, H, 3D] QKV projections and
 // their packed gradient are read/written in place (no split copies, no concat of dq/dk/dv)
 
@@ -488,61 +522,67 @@ __global__ __launch_bounds__(NT2) void fa_fwd_v2_kernel(const T* __restrict__ Q,
 // registers, no ds_write), the mask folded into the score accumulators' initial values (-inf where
 // masked: the max / exp loops have no selects), lane-offset + immediate LDS addressing and the
 // K-row reads issued ahead of the QK^T MFMAs.
-template <typename T, bool CAUSAL>
+template <typename T, bool CAUSAL, bool PERSIST = false>
 __global__ __launch_bounds__(NT2) void fa_fwd_v3_kernel(const T* __restrict__ Q, const T* __restrict__ K,
                                                         const T* __restrict__ V, T* __restrict__ O,
                                                         float* __restrict__ LSE, int S, int Sk, int H, int Hk,
-                                                        float scale_log2, FaStrides fs) {
+                                                        float scale_log2, FaStrides fs, int BH = 0) {
   typedef typename MF<T>::frag frag;
   constexpr int ND = 4, NK = 8;
   constexpr int TILE = BN * 128 * 2;                 // 16 KiB per K or V tile
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * TILE];
+  constexpr int QIMG = PERSIST ? BM2 * 256 : 0;      // persistent form: the next item's Q block
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * TILE + QIMG];
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5,
             lr = lane & 31;
   const int nqb = (S + BM2 - 1) / BM2;
-  int bh, rank;
-  fa_block(gridDim.x * gridDim.y / nqb, nqb, fs.order_g, bh, rank);
-  const int qb = CAUSAL ? (nqb - 1 - rank) : rank;
-  const int head = bh % H, b = bh / H;
-  const int hk = head / (H / Hk);
-  const int q0 = qb * BM2;
-  const int q = q0 + wid * 32 + lr;
+  const int nitems = BH * nqb, nwg = gridDim.x;
+  int item = blockIdx.x;
+  if (PERSIST && item >= nitems) return;
   const long qstride = fs.q_tok, kstride = fs.kv_tok;
-  const T* Qb = Q + ((long)b * S) * qstride + (long)head * fs.q_head;
-  const T* Kb = K + ((long)b * Sk) * kstride + (long)hk * fs.kv_head;
-  const T* Vb = V + ((long)b * Sk) * kstride + (long)hk * fs.kv_head;
 
-  frag qf[NK];
-#pragma unroll
-  for (int kk = 0; kk < NK; ++kk) {
-    u32x4 v = {0, 0, 0, 0};
-    if (q < S) v = *reinterpret_cast<const u32x4*>(Qb + (long)q * qstride + 16 * kk + 8 * h);
-    qf[kk] = as_frag<frag>(v);
-  }
-  f32x16 o[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) o[i] = zero16();
-  float m_run = -INFINITY, l_run = 0.f;
-
-  int kend = Sk;
-  if (CAUSAL) kend = min(Sk, q0 + BM2);
-  const int ntile = (kend + BN - 1) / BN;
-  const int wave_q0 = q0 + wid * 32, wave_qmax = wave_q0 + 31;
+  // one item = one (b, h) pair's 256-row query block
+  struct Item {
+    int b, head, q0, ntile;
+    const T *Qb, *Kb, *Vb;
+  };
+  auto decode = [&](int id, bool plain) {
+    int bh, rank;
+    if (plain) fa_block(gridDim.x * gridDim.y / nqb, nqb, fs.order_g, bh, rank);
+    else fa_item(id, BH, bh, rank);
+    Item it;
+    const int qb = CAUSAL ? (nqb - 1 - rank) : rank;
+    it.head = bh % H;
+    it.b = bh / H;
+    const int hk = it.head / (H / Hk);
+    it.q0 = qb * BM2;
+    it.Qb = Q + ((long)it.b * S) * qstride + (long)it.head * fs.q_head;
+    it.Kb = K + ((long)it.b * Sk) * kstride + (long)hk * fs.kv_head;
+    it.Vb = V + ((long)it.b * Sk) * kstride + (long)hk * fs.kv_head;
+    int kend = Sk;
+    if (CAUSAL) kend = min(Sk, it.q0 + BM2);
+    it.ntile = (kend + BN - 1) / BN;
+    return it;
+  };
+  Item ci = decode(item, !PERSIST);
 
   // K / V tile by LDS-DMA: 32 1-KiB pieces (4 rows of one operand), 4 per wave; K rows swizzled as
   // k_lds_off (chunk ^ row & 15), V rows as v_lds_off (the tr-read image)
-  auto load_tile = [&](int k0, int buf) {
+  auto load_tile = [&](const Item& it, int k0, int buf) {
     const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)(smem + buf * 2 * TILE);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int gidx = wid * 4 + u, which = gidx >> 4;
       const int row = (gidx & 15) * 4 + (lane >> 4);
       const int ch = (lane & 15) ^ (which ? (((row & 3) << 2) | ((row >> 2) & 3)) : (row & 15));
-      const T* base = (which ? Vb : Kb) + (long)k0 * kstride;
+      const T* base = (which ? it.Vb : it.Kb) + (long)k0 * kstride;
       const unsigned voff = (unsigned)(((long)(min(k0 + row, Sk - 1) - k0) * kstride + ch * 8) * 2);
       fa_glds16(voff, base, __builtin_amdgcn_readfirstlane(lds + which * TILE + (gidx & 15) * 1024));
     }
+  };
+  auto load_q = [&](const Item& it) {   // PERSIST: the item's Q block into the image behind the ring
+    const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)(smem + 4 * TILE);
+    fa_block_to_lds<T>(it.Qb, qstride, it.q0, S, lds, wid, lane);
   };
 
   const int g = lane >> 4, gi = lane & 15, tq = gi >> 2, tp = gi & 3;
@@ -556,138 +596,203 @@ __global__ __launch_bounds__(NT2) void fa_fwd_v3_kernel(const T* __restrict__ Q,
       troff[db][hi] = (4 * h + tq) * 256 + hi * 2048 +
                       16 * (4 * (db ^ tq) + ((2 * (g & 1) + (tp >> 1)) ^ ((h + 2 * hi) & 3))) + 8 * (tp & 1);
 
-  if (ntile > 0) {
-    load_tile(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
   // wave priorities (fs.prio): the two waves of a SIMD (w, w + 4) otherwise reach their MFMA and
   // softmax phases together after every barrier; a priority skew lets one wave's exp / pack VALU
   // issue under the other's MFMAs
-  if (fs.prio == 1 && wid < 4) __builtin_amdgcn_s_setprio(1);
   const bool dyn_prio = fs.prio == 2;
-  for (int t = 0; t < ntile; ++t) {
-    const int k0 = t * BN;
-    const int cur = t & 1;
-    if (t + 1 < ntile) load_tile(k0 + BN, cur ^ 1);
-    const unsigned char* kl = smem + cur * 2 * TILE;
-    const unsigned char* vl = kl + TILE;
-    if (!(CAUSAL && k0 > wave_qmax)) {
-      if (dyn_prio) __builtin_amdgcn_s_setprio(1);
-      const bool need_mask = (k0 + BN > Sk) || (CAUSAL && k0 + BN - 1 > wave_q0);
-      f32x16 s[2];
-      s[0] = zero16();
-      s[1] = zero16();
-      if (need_mask) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          const int base = k0 + kb * 32 + 4 * h;
-          const int lim1 = CAUSAL ? q - base : 1 << 20, lim2 = Sk - base;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int rb = (r & 3) + 8 * (r >> 2);
-            s[kb][r] = ((rb > lim1) | (rb >= lim2)) ? -INFINITY : 0.f;
-          }
-        }
-      }
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int kk = 0; kk < NK; ++kk) {
-          const u32x4 a = *reinterpret_cast<const u32x4*>(kl + kb * 8192 + koff[kk]);
-          s[kb] = MF<T>::mma(as_frag<frag>(a), qf[kk], s[kb]);
-        }
-      if constexpr (kFwdGroups) {
-        __builtin_amdgcn_sched_group_barrier(0x100, kFwdAhead, 0);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (dyn_prio) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(0);
-      }
-      // scores unscaled (scale > 0: max(c s) = c max(s)); masked scores are -inf already
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[kb][r]);
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64)) * scale_log2;
-      constexpr float kThr = 8.f;
-      if (!__all(tmax <= m_run + kThr)) {
-        const float m_new = fmaxf(m_run, tmax);
-        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = fexp2(m_run - m_use);
-        l_run *= alpha;
-#pragma unroll
-        for (int i = 0; i < ND; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-        m_run = m_new;
-      }
-      const float m_use = (m_run == -INFINITY) ? 0.f : m_run;
-      float psum = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float p = fexp2(fmaf(s[kb][r], scale_log2, -m_use));
-          s[kb][r] = p;
-          psum += p;
-        }
-      psum += __shfl_xor(psum, 32, 64);
-      l_run += psum;
-      if (dyn_prio) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-      }
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const f32x16& sv = s[ks >> 1];
-        const int s8 = (ks & 1) * 8;
-        u32x4 pw;
-        pw[0] = MF<T>::pack(sv[s8 + 0], sv[s8 + 1]);
-        pw[1] = MF<T>::pack(sv[s8 + 2], sv[s8 + 3]);
-        pw[2] = MF<T>::pack(sv[s8 + 4], sv[s8 + 5]);
-        pw[3] = MF<T>::pack(sv[s8 + 6], sv[s8 + 7]);
-        const frag pf = as_frag<frag>(pw);
-#pragma unroll
-        for (int db = 0; db < ND; ++db) {
-          const u32x2 lo = ds_read_tr16(vl + ks * 4096 + troff[db][0]);
-          const u32x2 hi = ds_read_tr16(vl + ks * 4096 + troff[db][1]);
-          o[db] = MF<T>::mma(as_frag<frag>(u32x4{lo[0], lo[1], hi[0], hi[1]}), pf, o[db]);
-        }
-      }
-      if (dyn_prio) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(0);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA'd tile has landed (asm: untracked)
+  int slot0 = 0;   // ring slot of the item's tile 0 (persistent: carried over the seam)
+  if (PERSIST) load_q(ci);
+  if (ci.ntile > 0) load_tile(ci, 0, 0);
+  if (PERSIST || ci.ntile > 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
+  if (fs.prio == 1 && wid < 4) __builtin_amdgcn_s_setprio(1);
 
-  if (q < S) {
-    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-    T* orow = O + ((long)b * S + q) * fs.o_tok + (long)head * fs.o_head;
+  for (;;) {
+    const int q0 = ci.q0, ntile = ci.ntile;
+    const int q = q0 + wid * 32 + lr;
+    frag qf[NK];
+    if constexpr (PERSIST) {
+      // the Q block landed behind the previous item's last tile (vmcnt + barrier there); rows
+      // past S read as zero like the plain form's
+      const unsigned char* qi = smem + 4 * TILE + wid * 8192;
 #pragma unroll
-    for (int db = 0; db < ND; ++db)
-#pragma unroll
-      for (int gg = 0; gg < 4; ++gg) {
-        const int d = db * 32 + 8 * gg + 4 * h;
-        u32x2 w;
-        w[0] = MF<T>::pack(o[db][4 * gg + 0] * inv, o[db][4 * gg + 1] * inv);
-        w[1] = MF<T>::pack(o[db][4 * gg + 2] * inv, o[db][4 * gg + 3] * inv);
-        *reinterpret_cast<u32x2*>(orow + d) = w;
+      for (int kk = 0; kk < NK; ++kk) {
+        u32x4 v = *reinterpret_cast<const u32x4*>(qi + koff[kk]);
+        if (q >= S) v = u32x4{0, 0, 0, 0};
+        qf[kk] = as_frag<frag>(v);
       }
-    if (h == 0) {
-      const float lse = (l_run > 0.f) ? (m_run + log2f(l_run)) * kLn2 : INFINITY;
-      LSE[((long)b * H + head) * S + q] = lse;
+      // a single-tile item requests the next Q block in its only tile: every wave must have read
+      // this one first (longer items have tile 0's barrier in between)
+      if (ntile <= 1) __syncthreads();
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < NK; ++kk) {
+        u32x4 v = {0, 0, 0, 0};
+        if (q < S) v = *reinterpret_cast<const u32x4*>(ci.Qb + (long)q * qstride + 16 * kk + 8 * h);
+        qf[kk] = as_frag<frag>(v);
+      }
     }
+    f32x16 o[ND];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) o[i] = zero16();
+    float m_run = -INFINITY, l_run = 0.f;
+    const int wave_q0 = q0 + wid * 32, wave_qmax = wave_q0 + 31;
+    const bool has_next = PERSIST && item + nwg < nitems;
+
+    for (int t = 0; t < ntile; ++t) {
+      const int k0 = t * BN;
+      const int cur = (t & 1) ^ slot0;
+      if (t + 1 < ntile) load_tile(ci, k0 + BN, cur ^ 1);
+      else if (has_next) {
+        // seam: the next item's Q block and tile 0 fly under this item's last tile (every item
+        // has one: the host rejects Sk < 1); the slot cur ^ 1 was last read in tile t - 1, behind
+        // its barrier
+        const Item ni = decode(item + nwg, false);
+        load_q(ni);
+        load_tile(ni, 0, cur ^ 1);
+      }
+      const unsigned char* kl = smem + cur * 2 * TILE;
+      const unsigned char* vl = kl + TILE;
+      if (!(CAUSAL && k0 > wave_qmax)) {
+        if (dyn_prio) __builtin_amdgcn_s_setprio(1);
+        const bool need_mask = (k0 + BN > Sk) || (CAUSAL && k0 + BN - 1 > wave_q0);
+        f32x16 s[2];
+        s[0] = zero16();
+        s[1] = zero16();
+        if (need_mask) {
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb) {
+            const int base = k0 + kb * 32 + 4 * h;
+            const int lim1 = CAUSAL ? q - base : 1 << 20, lim2 = Sk - base;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int rb = (r & 3) + 8 * (r >> 2);
+              s[kb][r] = ((rb > lim1) | (rb >= lim2)) ? -INFINITY : 0.f;
+            }
+          }
+        }
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int kk = 0; kk < NK; ++kk) {
+            const u32x4 a = *reinterpret_cast<const u32x4*>(kl + kb * 8192 + koff[kk]);
+            s[kb] = MF<T>::mma(as_frag<frag>(a), qf[kk], s[kb]);
+          }
+        if constexpr (kFwdGroups) {
+          __builtin_amdgcn_sched_group_barrier(0x100, kFwdAhead, 0);
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (dyn_prio) {
+          __builtin_amdgcn_sched_barrier(0);
+          __builtin_amdgcn_s_setprio(0);
+        }
+        // scores unscaled (scale > 0: max(c s) = c max(s)); masked scores are -inf already
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[kb][r]);
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64)) * scale_log2;
+        constexpr float kThr = 8.f;
+        if (!__all(tmax <= m_run + kThr)) {
+          const float m_new = fmaxf(m_run, tmax);
+          const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+          const float alpha = fexp2(m_run - m_use);
+          l_run *= alpha;
+#pragma unroll
+          for (int i = 0; i < ND; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
+          m_run = m_new;
+        }
+        const float m_use = (m_run == -INFINITY) ? 0.f : m_run;
+        float psum = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float p = fexp2(fmaf(s[kb][r], scale_log2, -m_use));
+            s[kb][r] = p;
+            psum += p;
+          }
+        psum += __shfl_xor(psum, 32, 64);
+        l_run += psum;
+        if (dyn_prio) {
+          __builtin_amdgcn_sched_barrier(0);
+          __builtin_amdgcn_s_setprio(1);
+        }
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          const f32x16& sv = s[ks >> 1];
+          const int s8 = (ks & 1) * 8;
+          u32x4 pw;
+          pw[0] = MF<T>::pack(sv[s8 + 0], sv[s8 + 1]);
+          pw[1] = MF<T>::pack(sv[s8 + 2], sv[s8 + 3]);
+          pw[2] = MF<T>::pack(sv[s8 + 4], sv[s8 + 5]);
+          pw[3] = MF<T>::pack(sv[s8 + 6], sv[s8 + 7]);
+          const frag pf = as_frag<frag>(pw);
+#pragma unroll
+          for (int db = 0; db < ND; ++db) {
+            const u32x2 lo = ds_read_tr16(vl + ks * 4096 + troff[db][0]);
+            const u32x2 hi = ds_read_tr16(vl + ks * 4096 + troff[db][1]);
+            o[db] = MF<T>::mma(as_frag<frag>(u32x4{lo[0], lo[1], hi[0], hi[1]}), pf, o[db]);
+          }
+        }
+        if (dyn_prio) {
+          __builtin_amdgcn_sched_barrier(0);
+          __builtin_amdgcn_s_setprio(0);
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA'd tile has landed (asm: untracked)
+      __syncthreads();
+    }
+    if (PERSIST) slot0 ^= ntile & 1;
+
+    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+    T* orow = O + ((long)ci.b * S + q) * fs.o_tok + (long)ci.head * fs.o_head;
+    if constexpr (PERSIST) {
+      // 16-byte stores: half the store instructions of the row-per-lane tail (the swaps need
+      // every lane, so they stay outside the row guard)
+#pragma unroll
+      for (int db = 0; db < ND; ++db)
+#pragma unroll
+        for (int gp = 0; gp < 2; ++gp) {
+          u32x2 w[2];
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int r = 4 * (2 * gp + e);
+            w[e][0] = MF<T>::pack(o[db][r + 0] * inv, o[db][r + 1] * inv);
+            w[e][1] = MF<T>::pack(o[db][r + 2] * inv, o[db][r + 3] * inv);
+          }
+          const u32x4 w4 = fa_pair16(w[0], w[1]);
+          if (q < S) *reinterpret_cast<u32x4*>(orow + db * 32 + 16 * gp + 8 * h) = w4;
+        }
+    } else if (q < S) {
+#pragma unroll
+      for (int db = 0; db < ND; ++db)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          const int d = db * 32 + 8 * gg + 4 * h;
+          u32x2 w;
+          w[0] = MF<T>::pack(o[db][4 * gg + 0] * inv, o[db][4 * gg + 1] * inv);
+          w[1] = MF<T>::pack(o[db][4 * gg + 2] * inv, o[db][4 * gg + 3] * inv);
+          *reinterpret_cast<u32x2*>(orow + d) = w;
+        }
+    }
+    if (q < S && h == 0) {
+      const float lse = (l_run > 0.f) ? (m_run + log2f(l_run)) * kLn2 : INFINITY;
+      LSE[((long)ci.b * H + ci.head) * S + q] = lse;
+    }
+    if (!has_next) break;
+    item += nwg;
+    ci = decode(item, false);
   }
 }
 
@@ -1777,12 +1882,12 @@ __device__ __forceinline__ void mma_vva(f32x16& d, const u32x4& a, const typenam
 //  * a 3-deep Q/dO ring (99 KB): the half pending from the previous tile still reads its buffer
 //    while the next tile is written, so one barrier per tile stays enough.
 // ============================================================================================
-template <typename T, bool CAUSAL>
+template <typename T, bool CAUSAL, bool PERSIST = false>
 __global__ __launch_bounds__(NTKV) __attribute__((amdgpu_waves_per_eu(1, 1))) void fa_bwd_dkdv_v3(const T* __restrict__ Q, const T* __restrict__ K,
                                                       const T* __restrict__ V, const T* __restrict__ dO,
                                                       const float* __restrict__ LSE, const float* __restrict__ DELTA,
                                                       T* __restrict__ dK, T* __restrict__ dV, int S, int Sk, int H,
-                                                      int Hk, float scale, FaStrides fs) {
+                                                      int Hk, float scale, FaStrides fs, int BH = 0) {
   typedef typename MF<T>::frag frag;
   constexpr int NK = 8, ND = 4, BQ = 64;
   constexpr int IMG = BQ * 256;                         // 16 KiB per operand image
@@ -1791,39 +1896,72 @@ __global__ __launch_bounds__(NTKV) __attribute__((amdgpu_waves_per_eu(1, 1))) vo
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5, lr = lane & 31;
   const int g = lane >> 4, gi = lane & 15, tq = gi >> 2, tp = gi & 3;
-  int bh, rank;
-  fa_block(gridDim.x * gridDim.y / ((Sk + NTKV / 2 - 1) / (NTKV / 2)), (Sk + NTKV / 2 - 1) / (NTKV / 2), fs.order_g, bh, rank);
-  const int head = bh % H, b = bh / H;
-  const int hk = head / (H / Hk);
-  const int k0 = rank * (NTKV / 2);
-  const int wk0 = k0 + wid * 32;
-  const int key = wk0 + lr;
+  // PERSIST: see fa_fwd_v3_kernel. One item = one (b, h) pair's 128-key block; the next item's
+  // first Q / dO tile goes into the ring under this item's last tile, and its K / V fragments are
+  // requested into the registers the last S / dP step has freed, ahead of the dK / dV stores.
+  const int nkb = (Sk + NTKV / 2 - 1) / (NTKV / 2);
+  const int nitems = BH * nkb, nwg = gridDim.x;
+  int item = blockIdx.x;
+  if (PERSIST && item >= nitems) return;
   const long kstride = fs.kv_tok;
-  const T* Qb = Q + (long)b * S * fs.q_tok + (long)head * fs.q_head;
-  const T* dOb = dO + (long)b * S * fs.o_tok + (long)head * fs.o_head;
-  const T* Kb = K + (long)b * Sk * kstride + (long)hk * fs.kv_head;
-  const T* Vb = V + (long)b * Sk * kstride + (long)hk * fs.kv_head;
-  const float* lse_b = LSE + ((long)b * H + head) * S;
-  const float* del_b = DELTA + ((long)b * H + head) * S;
   const float c2 = scale * kLog2e, nis = -1.f / scale;
 
-  const int keyc = min(key, Sk - 1);
+  struct Item {
+    int b, head, k0, qstart, ntile;
+    const T *Qb, *dOb, *Kb, *Vb;
+    const float *lse_b, *del_b;
+  };
+  auto decode = [&](int id, bool plain) {
+    int bh, rank;
+    if (plain) fa_block(gridDim.x * gridDim.y / nkb, nkb, fs.order_g, bh, rank);
+    else fa_item(id, BH, bh, rank);
+    Item it;
+    it.head = bh % H;
+    it.b = bh / H;
+    const int hk = it.head / (H / Hk);
+    it.k0 = rank * (NTKV / 2);
+    it.Qb = Q + (long)it.b * S * fs.q_tok + (long)it.head * fs.q_head;
+    it.dOb = dO + (long)it.b * S * fs.o_tok + (long)it.head * fs.o_head;
+    it.Kb = K + (long)it.b * Sk * kstride + (long)hk * fs.kv_head;
+    it.Vb = V + (long)it.b * Sk * kstride + (long)hk * fs.kv_head;
+    it.lse_b = LSE + ((long)it.b * H + it.head) * S;
+    it.del_b = DELTA + ((long)it.b * H + it.head) * S;
+    it.qstart = CAUSAL ? (it.k0 / BQ) * BQ : 0;
+    it.ntile = it.qstart < S ? (S - it.qstart + BQ - 1) / BQ : 0;
+    return it;
+  };
+  Item ci = decode(item, !PERSIST);
+
+  constexpr bool kKvAhead = CAUSAL;
   frag kf[NK], vf[NK];
+  auto load_kv = [&](const Item& it) {
+    const int keyc = min(it.k0 + wid * 32 + lr, Sk - 1);
 #pragma unroll
-  for (int kk = 0; kk < NK; ++kk) {
-    kf[kk] = as_frag<frag>(*reinterpret_cast<const u32x4*>(Kb + (long)keyc * kstride + 16 * kk + 8 * h));
-    vf[kk] = as_frag<frag>(*reinterpret_cast<const u32x4*>(Vb + (long)keyc * kstride + 16 * kk + 8 * h));
-  }
+    for (int kk = 0; kk < NK; ++kk) {
+      kf[kk] = as_frag<frag>(*reinterpret_cast<const u32x4*>(it.Kb + (long)keyc * kstride + 16 * kk + 8 * h));
+      vf[kk] = as_frag<frag>(*reinterpret_cast<const u32x4*>(it.Vb + (long)keyc * kstride + 16 * kk + 8 * h));
+    }
+  };
+  auto pin_kv = [&]() {   // an empty asm that wants the fragments in AGPRs: one copy here, none per use
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int kk = 0; kk < NK; ++kk) {
+      v4u a = __builtin_bit_cast(v4u, kf[kk]), c = __builtin_bit_cast(v4u, vf[kk]);
+      asm volatile("" : "+a"(a), "+a"(c));
+      kf[kk] = __builtin_bit_cast(frag, a);
+      vf[kk] = __builtin_bit_cast(frag, c);
+    }
+  };
+  load_kv(ci);
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): see fa_bwd_dkdv_v2
+  if constexpr (PERSIST) pin_kv();
   f32x16 dvt[ND], dkt[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) { dvt[i] = zero16(); dkt[i] = zero16(); }
 
   // Q / dO tiles by LDS-DMA (no staging registers): wave w issues the 1-KiB pieces w*8 .. w*8+7
   // (piece = 4 rows of one operand); lane l writes physical chunk l & 15 of row l >> 4, so it
   // fetches the logical chunk (l & 15) ^ swizzle(row) of dual_off's image
   float srow = 0.f;
-  auto load_tile = [&](int qt, int buf) {
+  auto load_tile = [&](const Item& it, int qt, int buf) {
     const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)(smem + buf * BUF);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -1831,11 +1969,11 @@ __global__ __launch_bounds__(NTKV) __attribute__((amdgpu_waves_per_eu(1, 1))) vo
       const int row = (gidx & 15) * 4 + (lane >> 4);
       const int ch = (lane & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3));
       const long rs = which ? fs.o_tok : fs.q_tok;
-      const T* base = (which ? dOb : Qb) + (long)qt * rs;
+      const T* base = (which ? it.dOb : it.Qb) + (long)qt * rs;
       const unsigned voff = (unsigned)(((long)(min(qt + row, S - 1) - qt) * rs + ch * 8) * 2);
       fa_glds16(voff, base, __builtin_amdgcn_readfirstlane(lds + which * IMG + (gidx & 15) * 1024));
     }
-    if (tid < 2 * BQ) srow = (tid < BQ ? lse_b : del_b)[min(qt + (tid & (BQ - 1)), S - 1)];
+    if (tid < 2 * BQ) srow = (tid < BQ ? it.lse_b : it.del_b)[min(qt + (tid & (BQ - 1)), S - 1)];
   };
   auto store_rc = [&](int buf) {   // row constants (the DMA'd images need no store)
     if (tid < 2 * BQ) reinterpret_cast<float*>(smem + buf * BUF + 2 * IMG)[tid] = tid < BQ ? srow * nis : -srow;
@@ -1849,10 +1987,8 @@ __global__ __launch_bounds__(NTKV) __attribute__((amdgpu_waves_per_eu(1, 1))) vo
   // path per half (the mask is a branch around the initial values only): step variants behind
   // branches made the register allocator spill the K / V fragments.
   u32x4 pw[2][2], dw[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { pw[i][j] = u32x4{0, 0, 0, 0}; dw[i][j] = u32x4{0, 0, 0, 0}; }
+  // per-item values the step reads (set at the top of the item loop)
+  int key = 0, wk0 = 0;
   // lane parts of the LDS read addresses; the parity / 16-row block / buffer parts are immediates
   // or one scalar base (dual_off's swizzle reduces to these for rows 32P + lr and the transposed
   // rows 32Q + 16 s2 + 4h + tq (+8))
@@ -1995,56 +2131,116 @@ __global__ __launch_bounds__(NTKV) __attribute__((amdgpu_waves_per_eu(1, 1))) vo
   using P1 = std::integral_constant<int, 1>;
   auto needm = [&](int qh) { return (qh + 32 > S) || (wk0 + 32 > Sk) || (CAUSAL && wk0 + 31 > qh); };
 
-  const int qstart = CAUSAL ? (k0 / BQ) * BQ : 0;
-  const int ntile = qstart < S ? (S - qstart + BQ - 1) / BQ : 0;
-  if (ntile > 0) {
-    load_tile(qstart, 0);
-    store_rc(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  // halves whose keys all follow all their queries are skipped (causal, at the start only); the
-  // first step's C then multiplies the zero-initialised pw / dw (adds nothing)
-  bool pend = false;
-  const unsigned char* pimg = smem;
   int buf = 0;
-  for (int t = 0; t < ntile; ++t) {
-    const int qt = qstart + t * BQ;
-    const int nbuf = buf == 2 ? 0 : buf + 1;
-    if (t + 1 < ntile) load_tile(qt + BQ, nbuf);
-    const unsigned char* img = smem + buf * BUF;
-    if (!(CAUSAL && wk0 > qt + 31)) {
-      step(P0{}, yes{}, img, qt, needm(qt), pimg);
-      pend = true;
-      pimg = img;
+  bool pre = false;   // the item's first tile is already in ring slot buf (requested over the seam)
+  for (;;) {
+    const int b = ci.b, head = ci.head, k0 = ci.k0, qstart = ci.qstart, ntile = ci.ntile;
+    wk0 = k0 + wid * 32;
+    key = wk0 + lr;
+#pragma unroll
+    for (int i = 0; i < ND; ++i) { dvt[i] = zero16(); dkt[i] = zero16(); }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) { pw[i][j] = u32x4{0, 0, 0, 0}; dw[i][j] = u32x4{0, 0, 0, 0}; }
+    if (ntile > 0 && !pre) {
+      // slot buf is free: the previous item's pending half reads the slot before it
+      load_tile(ci, qstart, buf);
+      store_rc(buf);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
     }
-    if (!(CAUSAL && wk0 > qt + 63)) {
-      step(P1{}, yes{}, img, qt + 32, needm(qt + 32), pimg);
-      pend = true;
-      pimg = img;
+    const bool has_next = PERSIST && item + nwg < nitems;
+    pre = false;
+    // halves whose keys all follow all their queries are skipped (causal, at the start only); the
+    // first step's C then multiplies the zero-initialised pw / dw (adds nothing) with the finite
+    // operands of the item's first tile
+    bool pend = false;
+    const unsigned char* pimg = smem + buf * BUF;
+    for (int t = 0; t < ntile; ++t) {
+      const int qt = qstart + t * BQ;
+      const int nbuf = buf == 2 ? 0 : buf + 1;
+      bool staged = t + 1 < ntile;
+      if (staged) load_tile(ci, qt + BQ, nbuf);
+      else if (has_next) {
+        const Item ni = decode(item + nwg, false);
+        if (ni.ntile > 0) {
+          load_tile(ni, ni.qstart, nbuf);   // seam: the next item's first tile under this last one
+          staged = pre = true;
+        }
+      }
+      const unsigned char* img = smem + buf * BUF;
+      if (!(CAUSAL && wk0 > qt + 31)) {
+        step(P0{}, yes{}, img, qt, needm(qt), pimg);
+        pend = true;
+        pimg = img;
+      }
+      if (!(CAUSAL && wk0 > qt + 63)) {
+        step(P1{}, yes{}, img, qt + 32, needm(qt + 32), pimg);
+        pend = true;
+        pimg = img;
+      }
+      buf = nbuf;
+      if (staged) store_rc(buf);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA'd tile has landed (asm: untracked)
+      __syncthreads();
     }
-    buf = nbuf;
-    if (t + 1 < ntile) store_rc(buf);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA'd tile has landed (asm: untracked)
-    __syncthreads();
-  }
-  if (pend) step(P0{}, no{}, smem, 0, false, pimg);   // C of the last half (parity 1)
-  if (key < Sk) {
+    if (pend) step(P0{}, no{}, smem, 0, false, pimg);   // C of the last half (parity 1)
+    if constexpr (PERSIST) {
+      // K / V fragments of the next item into their (now dead) registers, requested ahead of the
+      // stores: vmcnt retires in issue order. Causal only: the non-causal kernel's allocation
+      // spills with the early request, so it fetches them at the top of the item instead.
+      __builtin_amdgcn_sched_barrier(0);
+      if (kKvAhead && has_next) load_kv(decode(item + nwg, false));
+      __builtin_amdgcn_sched_barrier(0);
+    }
     T* dkr = dK + ((long)b * Sk + key) * fs.dkv_tok + (long)head * fs.dkv_head;
     T* dvr = dV + ((long)b * Sk + key) * fs.dkv_tok + (long)head * fs.dkv_head;
+    if constexpr (PERSIST) {
 #pragma unroll
-    for (int db = 0; db < ND; ++db)
+      for (int db = 0; db < ND; ++db)
 #pragma unroll
-      for (int gg = 0; gg < 4; ++gg) {
-        const int d = db * 32 + 8 * gg + 4 * h;
-        u32x2 wk, wv;
-        wk[0] = MF<T>::pack(dkt[db][4 * gg + 0] * scale, dkt[db][4 * gg + 1] * scale);
-        wk[1] = MF<T>::pack(dkt[db][4 * gg + 2] * scale, dkt[db][4 * gg + 3] * scale);
-        wv[0] = MF<T>::pack(dvt[db][4 * gg + 0], dvt[db][4 * gg + 1]);
-        wv[1] = MF<T>::pack(dvt[db][4 * gg + 2], dvt[db][4 * gg + 3]);
-        *reinterpret_cast<u32x2*>(dkr + d) = wk;
-        *reinterpret_cast<u32x2*>(dvr + d) = wv;
-      }
+        for (int gp = 0; gp < 2; ++gp) {
+          u32x2 wk[2], wv[2];
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int r = 4 * (2 * gp + e);
+            wk[e][0] = MF<T>::pack(dkt[db][r + 0] * scale, dkt[db][r + 1] * scale);
+            wk[e][1] = MF<T>::pack(dkt[db][r + 2] * scale, dkt[db][r + 3] * scale);
+            wv[e][0] = MF<T>::pack(dvt[db][r + 0], dvt[db][r + 1]);
+            wv[e][1] = MF<T>::pack(dvt[db][r + 2], dvt[db][r + 3]);
+          }
+          const u32x4 k4 = fa_pair16(wk[0], wk[1]), v4 = fa_pair16(wv[0], wv[1]);
+          if (key < Sk) {
+            *reinterpret_cast<u32x4*>(dkr + db * 32 + 16 * gp + 8 * h) = k4;
+            *reinterpret_cast<u32x4*>(dvr + db * 32 + 16 * gp + 8 * h) = v4;
+          }
+        }
+    } else if (key < Sk) {
+#pragma unroll
+      for (int db = 0; db < ND; ++db)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          const int d = db * 32 + 8 * gg + 4 * h;
+          u32x2 wk, wv;
+          wk[0] = MF<T>::pack(dkt[db][4 * gg + 0] * scale, dkt[db][4 * gg + 1] * scale);
+          wk[1] = MF<T>::pack(dkt[db][4 * gg + 2] * scale, dkt[db][4 * gg + 3] * scale);
+          wv[0] = MF<T>::pack(dvt[db][4 * gg + 0], dvt[db][4 * gg + 1]);
+          wv[1] = MF<T>::pack(dvt[db][4 * gg + 2], dvt[db][4 * gg + 3]);
+          *reinterpret_cast<u32x2*>(dkr + d) = wk;
+          *reinterpret_cast<u32x2*>(dvr + d) = wv;
+        }
+    }
+    if constexpr (PERSIST) {
+      if (!kKvAhead && has_next) load_kv(decode(item + nwg, false));
+      // the fragment loads retire here (see fa_bwd_dkdv_v2), on every path to the loop head, not
+      // inside the tile loop; pinned to AGPRs so the steps' MFMAs read them with no copies
+      __builtin_amdgcn_s_waitcnt(0x0F70);
+      pin_kv();
+    }
+    if (!has_next) break;
+    item += nwg;
+    ci = decode(item, false);
   }
 }
 
@@ -2052,84 +2248,75 @@ __global__ __launch_bounds__(NTKV) __attribute__((amdgpu_waves_per_eu(1, 1))) vo
 // ds_write), the mask folded into the S^T chain's initial accumulator (-inf where masked, so the
 // probability loop is one code path with no selects), and each 32-key block's 16 row reads issued
 // ahead of its MFMAs (one LDS latency per block).
-template <typename T, bool CAUSAL>
+template <typename T, bool CAUSAL, bool PERSIST = false>
 // Od (optional): the forward output — delta = rowsum(dO * O) is then formed here from the dO
 // fragments already in registers and stored to DELTA for the dK/dV kernel launched after this one
 // (no separate preprocess pass re-reading dO).
+// PERSIST: see fa_fwd_v3_kernel. The next item's Q block and K / V tile 0 arrive by LDS-DMA under
+// the last tile; its dO (and O) rows are read directly at the seam, requested ahead of the dQ
+// stores (Q + dO do not both fit beside the ring).
 __global__ __launch_bounds__(NT2) void fa_bwd_dq_v3(const T* __restrict__ Q, const T* __restrict__ K,
                                                     const T* __restrict__ V, const T* __restrict__ dO,
                                                     const float* __restrict__ LSE, float* __restrict__ DELTA,
                                                     T* __restrict__ dQ, int S, int Sk, int H, int Hk, float scale, FaStrides fs,
-                                                    const T* __restrict__ Od = nullptr) {
+                                                    const T* __restrict__ Od = nullptr, int BH = 0) {
   typedef typename MF<T>::frag frag;
   constexpr int NK = 8, ND = 4;
   constexpr int IMG = BN * 256;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * IMG];
+  constexpr int QIMG = PERSIST ? BM2 * 256 : 0;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * IMG + QIMG];
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5,
             lr = lane & 31;
   const int g = lane >> 4, gi = lane & 15, tq = gi >> 2, tp = gi & 3;
   const int nqb = (S + BM2 - 1) / BM2;
-  int bh, rank;
-  fa_block(gridDim.x * gridDim.y / nqb, nqb, fs.order_g, bh, rank);
-  const int qb = CAUSAL ? (nqb - 1 - rank) : rank;
-  const int head = bh % H, b = bh / H;
-  const int hk = head / (H / Hk);
-  const int q0 = qb * BM2;
-  const int wq0 = q0 + wid * 32;
-  const int q = wq0 + lr;
+  const int nitems = BH * nqb, nwg = gridDim.x;
+  int item = blockIdx.x;
+  if (PERSIST && item >= nitems) return;
   const long kstride = fs.kv_tok;
-  const T* Qb = Q + (long)b * S * fs.q_tok + (long)head * fs.q_head;
-  const T* dOb = dO + (long)b * S * fs.o_tok + (long)head * fs.o_head;
-  const T* Kb = K + (long)b * Sk * kstride + (long)hk * fs.kv_head;
-  const T* Vb = V + (long)b * Sk * kstride + (long)hk * fs.kv_head;
   const float scale_log2 = scale * kLog2e;
-  const float lse2 = (q < S) ? LSE[((long)b * H + head) * S + q] * kLog2e : 0.f;
 
-  frag qf[NK], gf[NK];
-#pragma unroll
-  for (int kk = 0; kk < NK; ++kk) {
-    u32x4 a = {0, 0, 0, 0}, c = {0, 0, 0, 0};
-    if (q < S) {
-      a = *reinterpret_cast<const u32x4*>(Qb + (long)q * fs.q_tok + 16 * kk + 8 * h);
-      c = *reinterpret_cast<const u32x4*>(dOb + (long)q * fs.o_tok + 16 * kk + 8 * h);
-    }
-    qf[kk] = as_frag<frag>(a);
-    gf[kk] = as_frag<frag>(c);
-  }
-  float dlt;
-  if (Od) {   // O shares dO's strides (both dense [B, S, H, D] outputs)
-    const T* Ob = Od + (long)b * S * fs.o_tok + (long)head * fs.o_head;
-    float sdl = 0.f;
-    if (q < S) {
-#pragma unroll
-      for (int kk = 0; kk < NK; ++kk) {
-        const frag of = as_frag<frag>(*reinterpret_cast<const u32x4*>(Ob + (long)q * fs.o_tok + 16 * kk + 8 * h));
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sdl += (float)gf[kk][i] * (float)of[i];
-      }
-    }
-    dlt = sdl + __shfl_xor(sdl, 32, 64);
-    if (h == 0 && q < S) DELTA[((long)b * H + head) * S + q] = dlt;
-  } else {
-    dlt = (q < S) ? DELTA[((long)b * H + head) * S + q] : 0.f;
-  }
-  f32x16 dq[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) dq[i] = zero16();
+  struct Item {
+    int b, head, q0, ntile;
+    const T *Qb, *dOb, *Kb, *Vb;
+  };
+  auto decode = [&](int id, bool plain) {
+    int bh, rank;
+    if (plain) fa_block(gridDim.x * gridDim.y / nqb, nqb, fs.order_g, bh, rank);
+    else fa_item(id, BH, bh, rank);
+    Item it;
+    const int qb = CAUSAL ? (nqb - 1 - rank) : rank;
+    it.head = bh % H;
+    it.b = bh / H;
+    const int hk = it.head / (H / Hk);
+    it.q0 = qb * BM2;
+    it.Qb = Q + (long)it.b * S * fs.q_tok + (long)it.head * fs.q_head;
+    it.dOb = dO + (long)it.b * S * fs.o_tok + (long)it.head * fs.o_head;
+    it.Kb = K + (long)it.b * Sk * kstride + (long)hk * fs.kv_head;
+    it.Vb = V + (long)it.b * Sk * kstride + (long)hk * fs.kv_head;
+    int kend = Sk;
+    if (CAUSAL) kend = min(Sk, it.q0 + BM2);
+    it.ntile = (kend + BN - 1) / BN;
+    return it;
+  };
+  Item ci = decode(item, !PERSIST);
 
   // K / V tile (64 keys) by LDS-DMA: 32 1-KiB pieces (4 rows of one operand), 4 per wave
-  auto load_tile = [&](int k0, int buf) {
+  auto load_tile = [&](const Item& it, int k0, int buf) {
     const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)(smem + buf * 2 * IMG);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int gidx = wid * 4 + u, which = gidx >> 4;
       const int row = (gidx & 15) * 4 + (lane >> 4);
       const int ch = (lane & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3));
-      const T* base = (which ? Vb : Kb) + (long)k0 * kstride;
+      const T* base = (which ? it.Vb : it.Kb) + (long)k0 * kstride;
       const unsigned voff = (unsigned)(((long)(min(k0 + row, Sk - 1) - k0) * kstride + ch * 8) * 2);
       fa_glds16(voff, base, __builtin_amdgcn_readfirstlane(lds + which * IMG + (gidx & 15) * 1024));
     }
+  };
+  auto load_q = [&](const Item& it) {
+    const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)(smem + 4 * IMG);
+    fa_block_to_lds<T>(it.Qb, fs.q_tok, it.q0, S, lds, wid, lane);
   };
 
   // lane parts of the LDS addresses (see fa_bwd_dkdv_v3): key rows kb*32 + lr, transposed rows
@@ -2147,95 +2334,186 @@ __global__ __launch_bounds__(NT2) void fa_bwd_dq_v3(const T* __restrict__ Q, con
                         16 * (4 * (db ^ tq) + ((2 * (g & 1) + (tp >> 1)) ^ ((h + 2 * hi) & 3))) + 8 * (tp & 1);
   }
 
-  int kend = Sk;
-  if (CAUSAL) kend = min(Sk, q0 + BM2);
-  const int ntile = (kend + BN - 1) / BN;
-  if (ntile > 0) {
-    load_tile(0, 0);
+  // dO rows of an item straight from memory (zero past S)
+  frag qf[NK], gf[NK];
+  auto load_g = [&](const Item& it) {
+    const int q = it.q0 + wid * 32 + lr;
+#pragma unroll
+    for (int kk = 0; kk < NK; ++kk) {
+      u32x4 c = {0, 0, 0, 0};
+      if (q < S) c = *reinterpret_cast<const u32x4*>(it.dOb + (long)q * fs.o_tok + 16 * kk + 8 * h);
+      gf[kk] = as_frag<frag>(c);
+    }
+  };
+
+  int slot0 = 0;   // ring slot of the item's tile 0 (persistent: carried over the seam)
+  if (PERSIST) {
+    load_q(ci);
+    load_g(ci);
+  }
+  if (ci.ntile > 0) load_tile(ci, 0, 0);
+  if (PERSIST || ci.ntile > 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
   const float mval = scale_log2 > 0.f ? -INFINITY : INFINITY;   // exp2(mval * c) = 0 for either sign
   if (fs.prio != 0 && wid < 4) __builtin_amdgcn_s_setprio(1);   // see fa_fwd_v3_kernel
-  for (int t = 0; t < ntile; ++t) {
-    const int k0 = t * BN;
-    const int cur = t & 1;
-    if (t + 1 < ntile) load_tile(k0 + BN, cur ^ 1);
-    const unsigned char* k_img = smem + cur * 2 * IMG;
-    const unsigned char* v_img = k_img + IMG;
-    if (!(CAUSAL && k0 > wq0 + 31)) {
-      const bool need_mask = (k0 + BN > Sk) || (CAUSAL && k0 + BN - 1 > wq0);
-#pragma unroll 1
-      for (int kb = 0; kb < 2; ++kb) {
-        if (CAUSAL && k0 + kb * 32 > wq0 + 31) break;   // every key of the block after every query
-        f32x16 st = zero16(), dpt = zero16();
-        if (need_mask) {
-          // key k0 + 32kb + 4h + rowb(r): masked past Sk or (causal) after the lane's query
-          const int base = k0 + kb * 32 + 4 * h;
-          const int lim1 = CAUSAL ? q - base : 1 << 20, lim2 = Sk - base;
+
+  for (;;) {
+    const int q0 = ci.q0, ntile = ci.ntile, b = ci.b, head = ci.head;
+    const int wq0 = q0 + wid * 32;
+    const int q = wq0 + lr;
+    const float lse2 = (q < S) ? LSE[((long)b * H + head) * S + q] * kLog2e : 0.f;
+    if constexpr (PERSIST) {
+      const int qswz = lr * 256;
+      const unsigned char* qi = smem + 4 * IMG + wid * 8192 + qswz;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int rb = (r & 3) + 8 * (r >> 2);
-            st[r] = ((rb > lim1) | (rb >= lim2)) ? mval : 0.f;
-          }
+      for (int kk = 0; kk < NK; ++kk) {
+        u32x4 a = *reinterpret_cast<const u32x4*>(qi + 16 * ((2 * kk + h) ^ (lr & 15)));
+        if (q >= S) a = u32x4{0, 0, 0, 0};
+        qf[kk] = as_frag<frag>(a);
+      }
+      if (ntile <= 1) __syncthreads();   // see fa_fwd_v3_kernel
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < NK; ++kk) {
+        u32x4 a = {0, 0, 0, 0}, c = {0, 0, 0, 0};
+        if (q < S) {
+          a = *reinterpret_cast<const u32x4*>(ci.Qb + (long)q * fs.q_tok + 16 * kk + 8 * h);
+          c = *reinterpret_cast<const u32x4*>(ci.dOb + (long)q * fs.o_tok + 16 * kk + 8 * h);
         }
-        const unsigned char* kbi = k_img + kb * 8192;
-        const unsigned char* vbi = v_img + kb * 8192;
-#pragma unroll
-        for (int kk = 0; kk < NK; ++kk) {
-          const u32x4 ka = *reinterpret_cast<const u32x4*>(kbi + aoff[kk]);
-          const u32x4 va = *reinterpret_cast<const u32x4*>(vbi + aoff[kk]);
-          st = MF<T>::mma(as_frag<frag>(ka), qf[kk], st);
-          dpt = MF<T>::mma(as_frag<frag>(va), gf[kk], dpt);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float p = fexp2(fmaf(st[r], scale_log2, -lse2));
-          dpt[r] = p * (dpt[r] - dlt);
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const int s8 = s2 * 8;
-          u32x4 pw;
-          pw[0] = MF<T>::pack(dpt[s8 + 0], dpt[s8 + 1]);
-          pw[1] = MF<T>::pack(dpt[s8 + 2], dpt[s8 + 3]);
-          pw[2] = MF<T>::pack(dpt[s8 + 4], dpt[s8 + 5]);
-          pw[3] = MF<T>::pack(dpt[s8 + 6], dpt[s8 + 7]);
-          const frag pf = as_frag<frag>(pw);
-#pragma unroll
-          for (int db = 0; db < ND; ++db) {
-            const unsigned char* tb = kbi + s2 * 4096;
-            const u32x2 lo = ds_read_tr16(tb + troff[db][0]);
-            const u32x2 hi = ds_read_tr16(tb + troff[db][1]);
-            dq[db] = MF<T>::mma(as_frag<frag>(u32x4{lo[0], lo[1], hi[0], hi[1]}), pf, dq[db]);
-          }
-        }
-        if constexpr (kDqGroups) {
-          // the 16 row reads ahead of the S^T / dP^T MFMAs, the 16 transposed reads under them
-          __builtin_amdgcn_sched_group_barrier(0x100, kDqAhead, 0);
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, (32 - kDqAhead + 15) / 16, 0);
-          }
-        }
+        qf[kk] = as_frag<frag>(a);
+        gf[kk] = as_frag<frag>(c);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA'd tile has landed (asm: untracked)
-    __syncthreads();
-  }
-  if (q < S) {
-    T* qrow = dQ + ((long)b * S + q) * fs.dq_tok + (long)head * fs.dq_head;
+    float dlt;
+    if (Od) {   // O shares dO's strides (both dense [B, S, H, D] outputs)
+      const T* Ob = Od + (long)b * S * fs.o_tok + (long)head * fs.o_head;
+      float sdl = 0.f;
+      if (q < S) {
 #pragma unroll
-    for (int db = 0; db < ND; ++db)
+        for (int kk = 0; kk < NK; ++kk) {
+          const frag of = as_frag<frag>(*reinterpret_cast<const u32x4*>(Ob + (long)q * fs.o_tok + 16 * kk + 8 * h));
 #pragma unroll
-      for (int gg = 0; gg < 4; ++gg) {
-        const int d = db * 32 + 8 * gg + 4 * h;
-        u32x2 w;
-        w[0] = MF<T>::pack(dq[db][4 * gg + 0] * scale, dq[db][4 * gg + 1] * scale);
-        w[1] = MF<T>::pack(dq[db][4 * gg + 2] * scale, dq[db][4 * gg + 3] * scale);
-        *reinterpret_cast<u32x2*>(qrow + d) = w;
+          for (int i = 0; i < 8; ++i) sdl += (float)gf[kk][i] * (float)of[i];
+        }
       }
+      dlt = sdl + __shfl_xor(sdl, 32, 64);
+      if (h == 0 && q < S) DELTA[((long)b * H + head) * S + q] = dlt;
+    } else {
+      dlt = (q < S) ? DELTA[((long)b * H + head) * S + q] : 0.f;
+    }
+    f32x16 dq[ND];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) dq[i] = zero16();
+    const bool has_next = PERSIST && item + nwg < nitems;
+
+    for (int t = 0; t < ntile; ++t) {
+      const int k0 = t * BN;
+      const int cur = (t & 1) ^ slot0;
+      if (t + 1 < ntile) load_tile(ci, k0 + BN, cur ^ 1);
+      else if (has_next) {
+        const Item ni = decode(item + nwg, false);
+        load_q(ni);
+        load_tile(ni, 0, cur ^ 1);
+      }
+      const unsigned char* k_img = smem + cur * 2 * IMG;
+      const unsigned char* v_img = k_img + IMG;
+      if (!(CAUSAL && k0 > wq0 + 31)) {
+        const bool need_mask = (k0 + BN > Sk) || (CAUSAL && k0 + BN - 1 > wq0);
+#pragma unroll 1
+        for (int kb = 0; kb < 2; ++kb) {
+          if (CAUSAL && k0 + kb * 32 > wq0 + 31) break;   // every key of the block after every query
+          f32x16 st = zero16(), dpt = zero16();
+          if (need_mask) {
+            // key k0 + 32kb + 4h + rowb(r): masked past Sk or (causal) after the lane's query
+            const int base = k0 + kb * 32 + 4 * h;
+            const int lim1 = CAUSAL ? q - base : 1 << 20, lim2 = Sk - base;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int rb = (r & 3) + 8 * (r >> 2);
+              st[r] = ((rb > lim1) | (rb >= lim2)) ? mval : 0.f;
+            }
+          }
+          const unsigned char* kbi = k_img + kb * 8192;
+          const unsigned char* vbi = v_img + kb * 8192;
+#pragma unroll
+          for (int kk = 0; kk < NK; ++kk) {
+            const u32x4 ka = *reinterpret_cast<const u32x4*>(kbi + aoff[kk]);
+            const u32x4 va = *reinterpret_cast<const u32x4*>(vbi + aoff[kk]);
+            st = MF<T>::mma(as_frag<frag>(ka), qf[kk], st);
+            dpt = MF<T>::mma(as_frag<frag>(va), gf[kk], dpt);
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float p = fexp2(fmaf(st[r], scale_log2, -lse2));
+            dpt[r] = p * (dpt[r] - dlt);
+          }
+#pragma unroll
+          for (int s2 = 0; s2 < 2; ++s2) {
+            const int s8 = s2 * 8;
+            u32x4 pw;
+            pw[0] = MF<T>::pack(dpt[s8 + 0], dpt[s8 + 1]);
+            pw[1] = MF<T>::pack(dpt[s8 + 2], dpt[s8 + 3]);
+            pw[2] = MF<T>::pack(dpt[s8 + 4], dpt[s8 + 5]);
+            pw[3] = MF<T>::pack(dpt[s8 + 6], dpt[s8 + 7]);
+            const frag pf = as_frag<frag>(pw);
+#pragma unroll
+            for (int db = 0; db < ND; ++db) {
+              const unsigned char* tb = kbi + s2 * 4096;
+              const u32x2 lo = ds_read_tr16(tb + troff[db][0]);
+              const u32x2 hi = ds_read_tr16(tb + troff[db][1]);
+              dq[db] = MF<T>::mma(as_frag<frag>(u32x4{lo[0], lo[1], hi[0], hi[1]}), pf, dq[db]);
+            }
+          }
+          if constexpr (kDqGroups) {
+            // the 16 row reads ahead of the S^T / dP^T MFMAs, the 16 transposed reads under them
+            __builtin_amdgcn_sched_group_barrier(0x100, kDqAhead, 0);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x100, (32 - kDqAhead + 15) / 16, 0);
+            }
+          }
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA'd tile has landed (asm: untracked)
+      __syncthreads();
+    }
+    if (PERSIST) slot0 ^= ntile & 1;
+    T* qrow = dQ + ((long)b * S + q) * fs.dq_tok + (long)head * fs.dq_head;
+    if constexpr (PERSIST) {
+      if (has_next) load_g(decode(item + nwg, false));   // ahead of the stores: vmcnt retires in issue order
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int db = 0; db < ND; ++db)
+#pragma unroll
+        for (int gp = 0; gp < 2; ++gp) {
+          u32x2 w[2];
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int r = 4 * (2 * gp + e);
+            w[e][0] = MF<T>::pack(dq[db][r + 0] * scale, dq[db][r + 1] * scale);
+            w[e][1] = MF<T>::pack(dq[db][r + 2] * scale, dq[db][r + 3] * scale);
+          }
+          const u32x4 w4 = fa_pair16(w[0], w[1]);
+          if (q < S) *reinterpret_cast<u32x4*>(qrow + db * 32 + 16 * gp + 8 * h) = w4;
+        }
+    } else if (q < S) {
+#pragma unroll
+      for (int db = 0; db < ND; ++db)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          const int d = db * 32 + 8 * gg + 4 * h;
+          u32x2 w;
+          w[0] = MF<T>::pack(dq[db][4 * gg + 0] * scale, dq[db][4 * gg + 1] * scale);
+          w[1] = MF<T>::pack(dq[db][4 * gg + 2] * scale, dq[db][4 * gg + 3] * scale);
+          *reinterpret_cast<u32x2*>(qrow + d) = w;
+        }
+    }
+    if (!has_next) break;
+    item += nwg;
+    ci = decode(item, false);
   }
 }
 
@@ -2423,6 +2701,35 @@ int fa_order_g() {  // PHA_FA_ORDER_G: blocks of one (b, h) kept together per XC
   return e ? atoi(e) : 0;   // measured: G = 0 fastest (0.923 ms bwd; G = 4: 1.036 ms)
 }
 
+// PHA_FA_PERSIST: which of the default D = 128 kernels launch in the persistent form (bit 0 the
+// forward, bit 1 dQ, bit 2 dK/dV); 0 selects the one-workgroup-per-block grid (A/B comparisons)
+constexpr int kPersistFwd = 1, kPersistDq = 2, kPersistDkdv = 4;
+int fa_persist() {
+  const char* e = getenv("PHA_FA_PERSIST");
+  return e ? atoi(e) : (kPersistFwd | kPersistDq | kPersistDkdv);
+}
+
+// Workgroups of a persistent launch: one per CU (every one of these kernels fills a CU), never
+// more than there are items. The CU count is a device attribute, read once per device (no stream
+// work: safe under graph capture). PHA_FA_PERSIST_WGS overrides the count (tests: several items
+// per workgroup, or idle workgroups, at small shapes).
+int fa_persist_wgs(long items) {
+  static int cus[64] = {0};
+  long n = 0;
+  if (const char* e = getenv("PHA_FA_PERSIST_WGS")) n = atol(e);
+  if (n <= 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (cus[dev] == 0) {
+      int c = 0;
+      if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
+      cus[dev] = c;
+    }
+    n = cus[dev] < items ? cus[dev] : items;   // min(items, CUs)
+  }
+  return (int)(n < 1 ? 1 : (n > 65535 ? 65535 : n));
+}
+
 bool fwd_v2_enabled() {  // PHA_FA_FWD_V1=1 selects the 4-wave kernel (A/B comparisons)
   const char* e = getenv("PHA_FA_FWD_V1");
   return !(e && e[0] == '1');
@@ -2445,6 +2752,13 @@ int launch_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
         hipLaunchKernelGGL((fa_fwd_v4_kernel<T, true>), g2, dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse, S, Sk, H, Hk, sl, fs);
       else
         hipLaunchKernelGGL((fa_fwd_v4_kernel<T, false>), g2, dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse, S, Sk, H, Hk, sl, fs);
+    } else if (fwd_v3() && (fa_persist() & kPersistFwd) && fs.order_g == 0) {
+      const int BH = B * H;
+      const dim3 gp(fa_persist_wgs((long)BH * g2.y));
+      if (causal)
+        hipLaunchKernelGGL((fa_fwd_v3_kernel<T, true, true>), gp, b2, 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse, S, Sk, H, Hk, sl, fs, BH);
+      else
+        hipLaunchKernelGGL((fa_fwd_v3_kernel<T, false, true>), gp, b2, 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse, S, Sk, H, Hk, sl, fs, BH);
     } else if (fwd_v3() && causal)
       hipLaunchKernelGGL((fa_fwd_v3_kernel<T, true>), g2, b2, 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse, S, Sk, H, Hk, sl, fs);
     else if (fwd_v3())
@@ -2475,10 +2789,29 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* dout, co
   if (fsp && !(D == 128 && bwd_v2_enabled())) return (int)hipErrorInvalidValue;
   if (D == 128 && bwd_v2_enabled()) {
     const dim3 gk2(B * H, (Sk + NTKV / 2 - 1) / (NTKV / 2)), gq2(B * H, (S + BM2 - 1) / BM2), b2(NT2), bk(NTKV);
+    const int BH = B * H, pers = fs.order_g == 0 ? fa_persist() : 0;
+    const dim3 gkp(fa_persist_wgs((long)BH * gk2.y)), gqp(fa_persist_wgs((long)BH * gq2.y));
+#define FB_DKDV(CC)                                                                                                \
+  do {                                                                                                             \
+    if (pers & kPersistDkdv)                                                                                       \
+      hipLaunchKernelGGL((fa_bwd_dkdv_v3<T, CC, true>), gkp, bk, 0, st, (const T*)q, (const T*)k, (const T*)v,    \
+                         (const T*)dout, lse, delta, (T*)dk, (T*)dv, S, Sk, H, Hk, scale, fs, BH);                 \
+    else                                                                                                           \
+      hipLaunchKernelGGL((fa_bwd_dkdv_v3<T, CC>), gk2, bk, 0, st, (const T*)q, (const T*)k, (const T*)v,          \
+                         (const T*)dout, lse, delta, (T*)dk, (T*)dv, S, Sk, H, Hk, scale, fs);         \
+  } while (0)
+#define FB_DQ(CC, OD)                                                                                              \
+  do {                                                                                                             \
+    if (pers & kPersistDq)                                                                                         \
+      hipLaunchKernelGGL((fa_bwd_dq_v3<T, CC, true>), gqp, b2, 0, st, (const T*)q, (const T*)k, (const T*)v,      \
+                         (const T*)dout, lse, const_cast<float*>(delta), (T*)dq, S, Sk, H, Hk, scale, fs, OD, BH); \
+    else                                                                                                           \
+      hipLaunchKernelGGL((fa_bwd_dq_v3<T, CC>), gq2, b2, 0, st, (const T*)q, (const T*)k, (const T*)v,            \
+                         (const T*)dout, lse, const_cast<float*>(delta), (T*)dq, S, Sk, H, Hk, scale, fs, OD); \
+  } while (0)
 #define FB2(CC)                                                                                                    \
     if (dkdv_v3())                                                                                                 \
-      hipLaunchKernelGGL((fa_bwd_dkdv_v3<T, CC>), gk2, bk, 0, st, (const T*)q, (const T*)k, (const T*)v,          \
-                         (const T*)dout, lse, delta, (T*)dk, (T*)dv, S, Sk, H, Hk, scale, fs);                     \
+      FB_DKDV(CC);                                                                                                 \
     else if (dkdv_ilp2())                                                                                          \
       hipLaunchKernelGGL((fa_bwd_dkdv_v2<T, CC, true>), gk2, bk, 0, st, (const T*)q, (const T*)k, (const T*)v,    \
                          (const T*)dout, lse, delta, (T*)dk, (T*)dv, S, Sk, H, Hk, scale, fs);                     \
@@ -2486,19 +2819,15 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* dout, co
     hipLaunchKernelGGL((fa_bwd_dkdv_v2<T, CC, false>), gk2, bk, 0, st, (const T*)q, (const T*)k, (const T*)v,            \
                        (const T*)dout, lse, delta, (T*)dk, (T*)dv, S, Sk, H, Hk, scale, fs);                       \
     if (dq_v3())                                                                                                   \
-      hipLaunchKernelGGL((fa_bwd_dq_v3<T, CC>), gq2, b2, 0, st, (const T*)q, (const T*)k, (const T*)v,            \
-                         (const T*)dout, lse, const_cast<float*>(delta), (T*)dq, S, Sk, H, Hk, scale, fs);        \
+      FB_DQ(CC, (const T*)nullptr);                                                                                       \
     else                                                                                                           \
       hipLaunchKernelGGL((fa_bwd_dq_v2<T, CC>), gq2, b2, 0, st, (const T*)q, (const T*)k, (const T*)v,            \
                          (const T*)dout, lse, delta, (T*)dq, S, Sk, H, Hk, scale, fs)
     if (o && dq_v3()) {   // delta formed inside dQ (launched first), then read by dK/dV
 #define FB3(CC)                                                                                                    \
-      hipLaunchKernelGGL((fa_bwd_dq_v3<T, CC>), gq2, b2, 0, st, (const T*)q, (const T*)k, (const T*)v,            \
-                         (const T*)dout, lse, const_cast<float*>(delta), (T*)dq, S, Sk, H, Hk, scale, fs,         \
-                         (const T*)o);                                                                             \
+      FB_DQ(CC, (const T*)o);                                                                                      \
       if (dkdv_v3())                                                                                               \
-        hipLaunchKernelGGL((fa_bwd_dkdv_v3<T, CC>), gk2, bk, 0, st, (const T*)q, (const T*)k, (const T*)v,        \
-                           (const T*)dout, lse, delta, (T*)dk, (T*)dv, S, Sk, H, Hk, scale, fs);                   \
+        FB_DKDV(CC);                                                                                               \
       else                                                                                                         \
         hipLaunchKernelGGL((fa_bwd_dkdv_v2<T, CC, true>), gk2, bk, 0, st, (const T*)q, (const T*)k, (const T*)v,  \
                            (const T*)dout, lse, delta, (T*)dk, (T*)dv, S, Sk, H, Hk, scale, fs)
@@ -2508,6 +2837,8 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* dout, co
     }
     if (causal) { FB2(true); } else { FB2(false); }
 #undef FB2
+#undef FB_DQ
+#undef FB_DKDV
     return (int)hipGetLastError();
   }
   const dim3 gkv((Sk + 127) / 128, H, B), gq((S + BM - 1) / BM, H, B), block(256);
