@@ -154,27 +154,12 @@ class DistributedFusedLamb(Lamb):
 
     def _fused_update(self, F, g, world, clip):
         """steps 2-3 as the lamb.hip kernels (clip scale, trust ratios and lr stay on the device)"""
-        from ctypes import c_float, c_int, c_long, c_void_p
-        from ...ops import _lib
-        L = _lib._load()
-        if not getattr(L, "_lamb_sig", False):
-            P = c_void_p
-            L.pha_lamb_sq.argtypes = [P, c_long, P, P, P]
-            L.pha_lamb_moment.argtypes = [P, P, P, P, P, P, P, c_int, c_long] + [c_float] * 7 + [P, P]
-            L.pha_lamb_apply.argtypes = [P, P, P, P, P, c_int, c_long, c_float, P, P]
-            L._lamb_sig = True
+        from ...ops import hip
         dev = g.device
-        st = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: c_void_p(0 if t is None else t.data_ptr())   # noqa: E731
-        n = F["shard"]
         g = g.contiguous()
         gsq = None
         if clip > 0 and self._clip_after_allreduce:
-            part = torch.empty(8192, dtype=torch.float32, device=dev)
-            gsq = torch.empty(1, dtype=torch.float32, device=dev)
-            rc = L.pha_lamb_sq(ptr(g), n, ptr(part), ptr(gsq), st)
-            if rc:
-                raise RuntimeError(f"pha_lamb_sq failed ({rc})")
+            gsq = hip.lamb_sq(g)
             if world > 1:
                 dist.all_reduce(gsq)
         b1, b2 = self._beta1, self._beta2
@@ -182,17 +167,11 @@ class DistributedFusedLamb(Lamb):
         F["b2p"] *= b2
         npar = len(F["params"]) + 1
         norms = torch.zeros(2, npar, dtype=torch.float32, device=dev)
-        rc = L.pha_lamb_moment(ptr(g), ptr(F["m1"]), ptr(F["m2"]), ptr(F["master"]), ptr(F["pid32"]), ptr(F["wd"]),
-                               ptr(norms), npar, n, b1, b2, 1 - F["b1p"], 1 - F["b2p"], self._epsilon, 1.0,
-                               clip if gsq is not None else 0.0, ptr(gsq), st)
-        if rc:
-            raise RuntimeError(f"pha_lamb_moment failed ({rc})")
+        hip.lamb_moment(g, F["m1"], F["m2"], F["master"], F["pid32"], F["wd"], norms, b1, b2, 1 - F["b1p"],
+                        1 - F["b2p"], self._epsilon, 1.0, clip if gsq is not None else 0.0, gsq)
         if world > 1:
             dist.all_reduce(norms)
-        rc = L.pha_lamb_apply(ptr(F["master"]), ptr(g), ptr(F["pid32"]), ptr(norms), ptr(F["lr_ratio"]), npar, n,
-                              float(self.get_lr()), None, st)
-        if rc:
-            raise RuntimeError(f"pha_lamb_apply failed ({rc})")
+        hip.lamb_apply(F["master"], g, F["pid32"], norms, F["lr_ratio"], float(self.get_lr()))
 
     def _torch_update(self, F, g, world, clip):
         dev = g.device

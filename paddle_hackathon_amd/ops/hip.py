@@ -49,6 +49,9 @@ def _L():
             "pha_multi_tensor_adam": [I, I, P, P, I, F, F, F, F, F, F, F, I, P, P, P, P, P],
             "pha_multi_tensor_momentum": [I, I, P, P, I, F, F, F, I, P],
             "pha_multi_tensor_l2sq": [P, P, I, P, P, P],
+            "pha_lamb_sq": [P, LG, P, P, P],
+            "pha_lamb_moment": [P, P, P, P, P, P, P, I, LG, F, F, F, F, F, F, F, P, P],
+            "pha_lamb_apply": [P, P, P, P, P, I, LG, F, P, P],
             "pha_bn_num_blocks": [LG, I],
             "pha_bn_fwd_train": [I, P, P, P, LG, I, P, P, P, P, P, P, P, P, P, F, F, I, P, I, P],
             "pha_bn_apply": [I, P, P, P, LG, I, P, P, I, P],
@@ -573,6 +576,48 @@ def _tables_cached(tag, recs, device):
     return t
 
 
+def _flat_ok(fn, what, t, dev, n, dtype=None):
+    """One buffer a kernel walks as ``n`` flat elements through its raw pointer: attribute reads
+    only (this runs for every tensor on every step), ValueError before anything is launched."""
+    if dtype is None:
+        if t.dtype not in _DT:
+            raise ValueError(f"{fn}: {what} has dtype {t.dtype}; the kernels take float32, bfloat16 and float16")
+    elif t.dtype != dtype:
+        raise ValueError(f"{fn}: {what} must be {dtype}, got {t.dtype}")
+    if t.device != dev:
+        raise ValueError(f"{fn}: {what} is on {t.device}, expected {dev}")
+    if t.numel() != n:
+        raise ValueError(f"{fn}: {what} has {t.numel()} elements, expected {n}")
+    if not t.is_contiguous():
+        raise ValueError(f"{fn}: {what} is not contiguous (the kernel would walk its storage as if flat)")
+
+
+def _dev_scalar_ok(fn, what, t, dev):
+    if t is not None and (t.dtype != torch.float32 or t.device != dev or t.numel() < 1):
+        raise ValueError(f"{fn}: {what} must be a float32 scalar on {dev}")
+
+
+def _mt_precheck(fn, params, grads, states, masters):
+    """Preconditions of the multi-tensor optimizer kernels, for every entry that has a gradient:
+    parameter, gradient, state tensors and master are contiguous, on one device, of the
+    parameter's numel; state and master are fp32; parameter and gradient dtypes are in ``_DT``."""
+    dev = params[0].device
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: parameters are on {dev}; the kernels need device tensors")
+    for i, p in enumerate(params):
+        g = grads[i]
+        if g is None:
+            continue
+        n = p.numel()
+        _flat_ok(fn, f"params[{i}]", p, dev, n)
+        _flat_ok(fn, f"grads[{i}]", g, dev, n)
+        for name, st in states:
+            _flat_ok(fn, f"{name}[{i}]", st[i], dev, n, torch.float32)
+        if masters is not None and masters[i] is not None:
+            _flat_ok(fn, f"masters[{i}]", masters[i], dev, n, torch.float32)
+    return dev
+
+
 def multi_tensor_adam(params, grads, ms, vs, masters, lr, beta1, beta2, eps, step, weight_decay, decoupled,
                       lr_ratios, grad_scale, wds=None, gscale_dev=None, lr_dev=None, pow_dev=None):
     """gscale_dev: optional fp32 device scalar multiplied into every gradient as it is read (the
@@ -580,7 +625,12 @@ def multi_tensor_adam(params, grads, ms, vs, masters, lr, beta1, beta2, eps, ste
     scalars (learning rate; (beta1^t, beta2^t) before this update) read by the kernel instead of
     the host values — what a hipGraph-captured step needs so that replays advance."""
     L = _L()
-    dev = params[0].device
+    dev = _mt_precheck("multi_tensor_adam", params, grads, (("ms", ms), ("vs", vs)), masters)
+    _dev_scalar_ok("multi_tensor_adam", "gscale_dev", gscale_dev, dev)
+    _dev_scalar_ok("multi_tensor_adam", "lr_dev", lr_dev, dev)
+    if pow_dev is not None:
+        _dev_scalar_ok("multi_tensor_adam", "pow_dev[0]", pow_dev[0], dev)
+        _dev_scalar_ok("multi_tensor_adam", "pow_dev[1]", pow_dev[1], dev)
     items = []
     for i, p in enumerate(params):
         g = grads[i]
@@ -606,7 +656,7 @@ def multi_tensor_adam(params, grads, ms, vs, masters, lr, beta1, beta2, eps, ste
 
 def multi_tensor_momentum(params, grads, vels, masters, lr, mu, nesterov, weight_decay, lr_ratios, grad_scale, wds=None):
     L = _L()
-    dev = params[0].device
+    dev = _mt_precheck("multi_tensor_momentum", params, grads, (("vels", vels),), masters)
     items = []
     for i, p in enumerate(params):
         g = grads[i]
@@ -655,6 +705,76 @@ def multi_tensor_l2norm_sq(tensors):
     meta_d.record_stream(torch.cuda.current_stream(dev))
     ch_d.record_stream(torch.cuda.current_stream(dev))
     return out[0]
+
+
+# ----------------------------------------------------------------------------
+# LAMB over a flat fp32 shard (csrc/kernels/lamb.hip)
+# ----------------------------------------------------------------------------
+_LAMB_MAX_BLOCKS = 8192   # lamb.hip's grid_for(): the scratch lamb_sq needs
+
+
+def _lamb_tables_ok(fn, pid, n, dev, per_param):
+    """pid: int32 [n] element -> parameter id map; per_param: (name, tensor, numel) fp32 tables
+    indexed by it. The id VALUES must lie in [0, npar): that is the caller's contract (reading
+    them here would be a device sync per step)."""
+    _flat_ok(fn, "pid", pid, dev, n, torch.int32)
+    for name, t, numel in per_param:
+        _flat_ok(fn, name, t, dev, numel, torch.float32)
+
+
+def lamb_sq(g):
+    """Sum of squares of the flat fp32 gradient shard ``g`` as a [1] fp32 device tensor
+    (deterministic two-level reduction; the global-norm clip's input)."""
+    L = _L()
+    dev = g.device
+    if dev.type != "cuda":
+        raise ValueError(f"lamb_sq: g is on {dev}; the kernels need device tensors")
+    _flat_ok("lamb_sq", "g", g, dev, g.numel(), torch.float32)
+    part = torch.empty(_LAMB_MAX_BLOCKS, dtype=torch.float32, device=dev)
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    _check(L.pha_lamb_sq(_ptr(g), g.numel(), _ptr(part), _ptr(out), _stream(g)), "lamb_sq")
+    return out
+
+
+def lamb_moment(g, m1, m2, w, pid, wd, norms, b1, b2, bc1, bc2, eps, gmul=1.0, clip=0.0, gsq=None):
+    """In place over the shard: g *= gmul * clip / max(sqrt(gsq), clip) (the clip factor only when
+    ``clip`` > 0; ``gsq`` is then the all-reduced [1] square sum on the device), moments m1 / m2
+    (bias corrections bc = 1 - beta^t), the LAMB direction r written over ``g``, and the
+    per-parameter sums of w^2 and r^2 ADDED into ``norms`` ([2, npar] fp32, zeroed by the caller;
+    npar counts the padding slot, the last id)."""
+    L = _L()
+    fn = "lamb_moment"
+    dev, n = g.device, g.numel()
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: g is on {dev}; the kernels need device tensors")
+    for name, t in (("g", g), ("m1", m1), ("m2", m2), ("w", w)):
+        _flat_ok(fn, name, t, dev, n, torch.float32)
+    npar = wd.numel()
+    _lamb_tables_ok(fn, pid, n, dev, (("wd", wd, npar), ("norms", norms, 2 * npar)))
+    if clip > 0:
+        if gsq is None:
+            raise ValueError(f"{fn}: clip > 0 needs the gradient square sum gsq")
+        _dev_scalar_ok(fn, "gsq", gsq, dev)
+    _check(L.pha_lamb_moment(_ptr(g), _ptr(m1), _ptr(m2), _ptr(w), _ptr(pid), _ptr(wd), _ptr(norms), npar, n,
+                             float(b1), float(b2), float(bc1), float(bc2), float(eps), float(gmul),
+                             float(clip) if clip > 0 else 0.0, _ptr(gsq) if clip > 0 else None, _stream(g)), fn)
+
+
+def lamb_apply(w, r, pid, norms, lr_ratio, lr, lr_dev=None):
+    """w -= lr * lr_ratio[p] * trust[p] * r with trust = sqrt(norms[0, p] / norms[1, p]) (1 when
+    either sum is 0). ``lr_dev``: optional fp32 device scalar read instead of the host ``lr``."""
+    L = _L()
+    fn = "lamb_apply"
+    dev, n = w.device, w.numel()
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: w is on {dev}; the kernels need device tensors")
+    _flat_ok(fn, "w", w, dev, n, torch.float32)
+    _flat_ok(fn, "r", r, dev, n, torch.float32)
+    npar = lr_ratio.numel()
+    _lamb_tables_ok(fn, pid, n, dev, (("lr_ratio", lr_ratio, npar), ("norms", norms, 2 * npar)))
+    _dev_scalar_ok(fn, "lr_dev", lr_dev, dev)
+    _check(L.pha_lamb_apply(_ptr(w), _ptr(r), _ptr(pid), _ptr(norms), _ptr(lr_ratio), npar, n, float(lr),
+                            _ptr(lr_dev), _stream(w)), fn)
 
 
 # ----------------------------------------------------------------------------

@@ -320,6 +320,12 @@ class SGD(Optimizer):
                 p._t.copy_(m._t)
 
 
+def _flat_grad(g):
+    """The multi-tensor kernels walk a gradient's storage as flat memory. Autograd may hand back a
+    strided view (the [16, 1] gradient of a column sliced out of a wider product): densify it."""
+    return g if g.is_contiguous() else g.contiguous()
+
+
 class Momentum(Optimizer):
     def __init__(self, learning_rate=0.001, momentum=0.9, parameters=None, use_nesterov=False, weight_decay=None,
                  grad_clip=None, multi_precision=False, rescale_grad=1.0, name=None):
@@ -337,7 +343,7 @@ class Momentum(Optimizer):
                 g._t.add_(torch.sign(p._t) * wd)
                 wd = 0.0
             params.append(p._t)
-            grads.append(g._t)
+            grads.append(_flat_grad(g._t))
             vels.append(self._acc("velocity", p)._t)
             m = self._master(p)
             masters.append(None if m is None else m._t)
@@ -390,7 +396,7 @@ class Adam(Optimizer):
                 g._t.add_(torch.sign(p._t) * wd)
                 wd = 0.0
             params.append(p._t)
-            grads.append(g._t)
+            grads.append(_flat_grad(g._t))
             m1.append(self._acc("moment1", p)._t)
             m2.append(self._acc("moment2", p)._t)
             b1p = self._acc("beta1_pow_acc", p, fill=self._beta1, shape=[1])
