@@ -9,6 +9,8 @@ return values follow the reference exactly (qkv_weight [3, H, D, E]; cache_kv
 [2, B, H, S, D])."""
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn.functional as TF
 
@@ -169,6 +171,26 @@ def fused_multi_head_attention(x, qkv_weight, linear_weight, pre_layer_norm=Fals
     return _wrap(o)
 
 
+def _decode_kernel_ok(qkv, cache, mask, device_time_step, dropout_rate, training):
+    """whether one decode step's attention (qkv [B, 3, H, D], the layer's cache) runs on the split-KV
+    decode kernels (ops/hip.decode_attention). PHA_DECODE_ATTN=0 keeps the composite; on the GPU
+    every other reason to keep it is recorded as a fallback."""
+    if not qkv.is_cuda or os.environ.get("PHA_DECODE_ATTN", "1") == "0" or not _ops.fused._use_hip(qkv):
+        return False
+    if training and dropout_rate != 0.0:
+        reason = "attention dropout"
+    elif torch.is_grad_enabled() and qkv.requires_grad:
+        reason = "needs a gradient (the decode kernels have no backward; run generation under no_grad)"
+    elif not _ops.hip.decode_attn_supported(qkv, cache, mask, device_time_step):
+        reason = (f"{qkv.dtype} D={qkv.shape[-1]} cache {cache.dtype} {tuple(cache.shape)} "
+                  f"mask={None if mask is None else tuple(mask.shape)}")
+    else:
+        return True
+    from ...ops import fallback
+    fallback.note("decode_attention", reason + " -> composite on the flash kernels")
+    return False
+
+
 def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, linear_weights, linear_biases,
                             ffn_ln_scales, ffn_ln_biases, ffn1_weights, ffn1_biases, ffn2_weights, ffn2_biases,
                             pre_layer_norm=True, epsilon=1e-05, cache_kvs=None, time_step=None, attn_mask=None,
@@ -177,13 +199,22 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     """Stack of pre-LN decoder layers for generation. ``cache_kvs[i]`` is a preallocated
     [2, B, H, max_seq, D] buffer updated in place: context stage (time_step None) writes
     positions [0, S); decode stage (S == 1) writes position ``time_step`` and attends over
-    [0, time_step]."""
+    [0, time_step]. On the GPU (bf16 / fp16, head dim 32 / 64 / 128, no dropout, no gradient) the
+    decode stage's bias add, cache append and attention are one split-KV kernel pair
+    (csrc/kernels/decode_attn.hip); with ``time_step`` an int32 device tensor that step reads it on
+    the device, so it neither syncs the host nor changes shape and can be captured in a hipGraph.
+    PHA_DECODE_ATTN=0 keeps the composite."""
     h = _u(x)
     B, S, E = h.shape
-    ts = None
+    ts = ts_dev = None
     if time_step is not None:
-        ts = int(_u(time_step).reshape(-1)[0].item()) if isinstance(time_step, (Tensor, torch.Tensor)) else int(time_step)
+        t = _u(time_step)
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.numel() == 1:
+            ts_dev = t   # read by the decode kernel on the device; .item() only if a layer cannot use it
+        else:
+            ts = int(t.reshape(-1)[0].item()) if isinstance(t, torch.Tensor) else int(t)
     mask = _u(attn_mask)
+    decode = cache_kvs is not None and time_step is not None and S == 1
     for i in range(len(qkv_weights)):
         residual = h
         a = _ln(h, _u(ln_scales[i]), _u(ln_biases[i]), epsilon) if pre_layer_norm else h
@@ -194,26 +225,37 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         else:  # [E, 3, H, D]
             _, _, H, D = w.shape
             qkv = a.reshape(B * S, E) @ w.reshape(E, 3 * H * D)
-        if qkv_biases is not None and qkv_biases[i] is not None:
-            qkv = qkv + _u(qkv_biases[i]).reshape(-1)
-        qkv = qkv.reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
-        q, k, v = qkv[0], qkv[1], qkv[2]
-        causal = False
-        if cache_kvs is not None:
-            c = _u(cache_kvs[i])
-            if ts is None:
-                c[0, :, :, :S] = k
-                c[1, :, :, :S] = v
-                causal = mask is None
-            else:
-                c[0, :, :, ts:ts + S] = k
-                c[1, :, :, ts:ts + S] = v
-                k, v = c[0, :, :, :ts + S], c[1, :, :, :ts + S]
-        m = mask
-        if m is not None and m.shape[-1] != k.shape[2]:
-            m = m[..., :k.shape[2]]
-        o = _attention(q, k, v, m, dropout_rate, training, mode, causal=causal and S > 1)
-        o = o.transpose(1, 2).reshape(B, S, H * D)
+        qb = _u(qkv_biases[i]) if qkv_biases is not None and qkv_biases[i] is not None else None
+        if decode and _decode_kernel_ok(qkv.reshape(B, 3, H, D), _u(cache_kvs[i]), mask, ts_dev is not None,
+                                        dropout_rate, training):
+            # one split-KV kernel pair: bias add, cache append and attention over [0, time_step]
+            if qb is not None and (qb.dtype != qkv.dtype or not qb.is_contiguous()):
+                qb = qb.to(qkv.dtype).contiguous()
+            o = _ops.hip.decode_attention(qkv.reshape(B, 3, H, D), None if qb is None else qb.reshape(3, H, D),
+                                          _u(cache_kvs[i]), ts_dev if ts_dev is not None else ts, mask)
+        else:
+            if ts_dev is not None and ts is None:
+                ts = int(ts_dev.item())
+            if qb is not None:
+                qkv = qkv + qb.reshape(-1)
+            qkv = qkv.reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
+            q, k, v = qkv[0], qkv[1], qkv[2]
+            causal = False
+            if cache_kvs is not None:
+                c = _u(cache_kvs[i])
+                if ts is None:
+                    c[0, :, :, :S] = k
+                    c[1, :, :, :S] = v
+                    causal = mask is None
+                else:
+                    c[0, :, :, ts:ts + S] = k
+                    c[1, :, :, ts:ts + S] = v
+                    k, v = c[0, :, :, :ts + S], c[1, :, :, :ts + S]
+            m = mask
+            if m is not None and m.shape[-1] != k.shape[2]:
+                m = m[..., :k.shape[2]]
+            o = _attention(q, k, v, m, dropout_rate, training, mode, causal=causal and S > 1)
+            o = o.transpose(1, 2).reshape(B, S, H * D)
         o = _linear(o, _u(linear_weights[i]), _u(linear_biases[i]) if linear_biases is not None else None)
         if ring_id >= 0:
             torch.distributed.all_reduce(o)

@@ -1208,3 +1208,118 @@ class FlashAttentionPacked(torch.autograd.Function):
                                                _ptr(dqkv), c_int(B), c_int(S), c_int(H), c_int(D), c_float(ctx.scale),
                                                c_int(int(ctx.causal)), _stream(qkv)), "flash_attn_bwd_packed")
         return dqkv, None, None
+
+
+# ----------------------------------------------------------------------------
+# split-KV decode attention (csrc/kernels/decode_attn.hip)
+# ----------------------------------------------------------------------------
+def _decode_attn_chunk():
+    L = _lib.lib
+    if L is None or not hasattr(L, "pha_decode_attn_chunk"):
+        return 0
+    L.pha_decode_attn_chunk.argtypes = []
+    L.pha_decode_attn_chunk.restype = c_int
+    return int(L.pha_decode_attn_chunk())
+
+
+DECODE_ATTN_CHUNK = _decode_attn_chunk()   # key positions per split (0: library not built)
+
+
+def decode_attn_supported(qkv, cache, mask=None, device_time_step=False):
+    """what the decode kernel takes: a bf16 / fp16 [B, 3, H, D] QKV product with D in 32 / 64 / 128,
+    a [2, B, H, max_seq, D] cache of the same dtype and device, and an optional additive / boolean
+    mask broadcastable to [B, H, 1, keys] that needs no gradient (with a device time step its key
+    dimension must span the whole cache, or be 1)"""
+    if not DECODE_ATTN_CHUNK or _lib.lib is None or not hasattr(_lib.lib, "pha_decode_attn"):
+        return False
+    if not (isinstance(qkv, torch.Tensor) and isinstance(cache, torch.Tensor) and qkv.is_cuda and cache.is_cuda):
+        return False
+    if qkv.dtype not in (torch.bfloat16, torch.float16) or cache.dtype != qkv.dtype or cache.device != qkv.device:
+        return False
+    if qkv.dim() != 4 or qkv.shape[1] != 3 or cache.dim() != 5:
+        return False
+    B, _, H, D = qkv.shape
+    if D not in (32, 64, 128) or B < 1 or H < 1 or B > 65535 or H > 65535:
+        return False
+    if tuple(cache.shape[:3]) != (2, B, H) or cache.shape[4] != D or cache.shape[3] < 1 or not cache.is_contiguous():
+        return False
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.requires_grad or mask.dim() > 4 or mask.dim() < 1:
+            return False
+        if mask.dim() >= 2 and mask.shape[-2] != 1:
+            return False
+        try:
+            torch.broadcast_shapes(tuple(mask.shape[:-1]) + (1,), (B, H, 1, 1))
+        except RuntimeError:
+            return False
+        if device_time_step and mask.shape[-1] != 1 and mask.shape[-1] < cache.shape[3]:
+            return False
+    return True
+
+
+def _decode_bias(mask, B, H, need, device):
+    """additive fp32 view [B, H, 1, keys] of ``mask`` (broadcast dims stride 0, keys contiguous,
+    at least ``need`` of them) and its (batch, head) element strides — _fa_bias for one query row"""
+    if mask.dtype == torch.bool:
+        mask = torch.zeros(mask.shape, dtype=torch.float32, device=device).masked_fill_(~mask.to(device), float("-inf"))
+    else:
+        mask = mask.to(device=device, dtype=torch.float32)
+    while mask.dim() < 4:
+        mask = mask.unsqueeze(0)
+    if mask.shape[-1] == 1:   # broadcast over keys: materialise the key dimension
+        mask = mask.expand(*mask.shape[:-1], need).contiguous()
+    elif mask.stride(-1) != 1:
+        mask = mask.contiguous()
+    if mask.shape[-1] < need:
+        raise ValueError(f"decode_attention: the mask covers {mask.shape[-1]} keys, the kernel may read {need}")
+    mask = mask.expand(B, H, 1, mask.shape[-1])
+    return mask, (mask.stride(0), mask.stride(1))
+
+
+def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
+    """One decode step of cached attention on the split-KV kernels. ``qkv`` [B, 3, H, D] is the raw
+    QKV product of the new token and ``qkv_bias`` [3, H, D] (or None) its bias; the biased key and
+    value are written to ``cache`` [2, B, H, max_seq, D] at ``time_step`` in place, and the biased,
+    scaled query attends over the positions [0, time_step]. ``time_step`` is a Python int (checked
+    here) or an int32 device tensor of one element read by the kernels (no host sync; out of range,
+    the cache is left alone and the output is NaN). Returns [B, 1, H * D]."""
+    fn = "decode_attention"
+    if not decode_attn_supported(qkv, cache, mask, isinstance(time_step, torch.Tensor)):
+        raise ValueError(f"{fn}: unsupported arguments (see decode_attn_supported)")
+    B, _, H, D = qkv.shape
+    max_seq = cache.shape[3]
+    dev = qkv.device
+    if not qkv.is_contiguous():
+        raise ValueError(f"{fn}: qkv is not contiguous")
+    if qkv_bias is not None:
+        if tuple(qkv_bias.shape) != (3, H, D) or qkv_bias.dtype != qkv.dtype or qkv_bias.device != dev \
+                or not qkv_bias.is_contiguous():
+            raise ValueError(f"{fn}: qkv_bias must be a contiguous {qkv.dtype} [3, {H}, {D}] tensor on {dev}")
+    ts, ts_dev = 0, None
+    if isinstance(time_step, torch.Tensor):
+        if time_step.dtype != torch.int32 or time_step.device != dev or time_step.numel() != 1:
+            raise ValueError(f"{fn}: a tensor time_step must be one int32 element on {dev}")
+        ts_dev = time_step
+    else:
+        ts = int(time_step)
+        if ts < 0 or ts >= max_seq:
+            raise ValueError(f"{fn}: time_step {ts} outside the cache's [0, {max_seq})")
+    bias, (sb, sh) = (None, (0, 0))
+    if mask is not None:
+        bias, (sb, sh) = _decode_bias(mask, B, H, max_seq if ts_dev is not None else ts + 1, dev)
+    tensors = [qkv, cache] + ([qkv_bias] if qkv_bias is not None else [])
+    if any(t.data_ptr() % 16 for t in tensors) or (bias is not None and bias.data_ptr() % 4):
+        raise ValueError(f"{fn}: qkv, qkv_bias and cache must be 16-byte aligned")
+    nsplit = -(-max_seq // DECODE_ATTN_CHUNK)
+    ws = torch.empty((B, H, nsplit, D + 2), dtype=torch.float32, device=dev)
+    out = torch.empty((B, 1, H * D), dtype=qkv.dtype, device=dev)
+    sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(D))
+    L = _L()
+    if not getattr(L, "_decode_attn_sig", False):
+        P, I, LG, F = c_void_p, c_int, c_long, c_float
+        L.pha_decode_attn.argtypes = [I, P, P, P, P, LG, LG, F, I, P, P, P, I, I, I, I, P]
+        L.pha_decode_attn.restype = c_int
+        L._decode_attn_sig = True
+    _check(L.pha_decode_attn(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc, ts,
+                             _ptr(ts_dev), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
+    return out
