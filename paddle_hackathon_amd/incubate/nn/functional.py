@@ -2,7 +2,11 @@
 fused_transformer.py, fused_matmul_bias.py).
 
 The reference fuses these into single CUDA ops; here each maps onto the MI355X kernel set:
-GEMMs on hipBLASLt (with the bias folded into the GEMM via ``addmm``), attention on the
+products with more than 16 rows (context stage, training) on hipBLASLt (with the bias folded into
+the GEMM via ``addmm``); products with at most 16 rows that need no gradient (the decode stage,
+small-batch ``fused_linear`` under ``no_grad``) on the weight-streaming kernels of
+csrc/kernels/skinny_gemm.hip, which take bias, GELU / ReLU and the residual add in their epilogue
+(``PHA_DECODE_GEMM=0`` keeps the library calls); attention on the
 MFMA flash-attention HIP kernel when there is no arbitrary additive mask (masked attention
 falls back to fused SDPA), LayerNorm / bias-GELU on the HIP kernels. Weight layouts and
 return values follow the reference exactly (qkv_weight [3, H, D, E]; cache_kv
@@ -52,8 +56,52 @@ def _act(x, bias, activation):
     raise ValueError(f"unsupported activation {activation}")
 
 
+def _skinny_ok(x2, w, w_is_nk, bias=None, residual=None):
+    """whether the product x2 [M, K] . w (+ bias, + residual) runs on the weight-streaming kernels
+    (ops/hip.skinny_gemm): a GPU tensor on the HIP path, at most 16 rows, nothing that needs a
+    gradient, and arguments the kernel takes. PHA_DECODE_GEMM=0 keeps the library call. More than 16
+    rows (context stage, training) is no fallback; with at most 16 rows on the GPU, arguments the
+    kernel cannot take are recorded as one (a shape class the measurements excluded is not)."""
+    if not (isinstance(x2, torch.Tensor) and x2.is_cuda and x2.dim() == 2 and isinstance(w, torch.Tensor)
+            and w.dim() == 2):
+        return False
+    if x2.shape[0] > _ops.hip.SKINNY_GEMM_MAX_M or x2.shape[0] < 1:
+        return False
+    if os.environ.get("PHA_DECODE_GEMM", "1") == "0" or not _ops.fused._use_hip(x2):
+        return False
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x2, w, bias, residual)):
+        return False
+    if _ops.hip.skinny_gemm_supported(x2, w, w_is_nk, bias, residual):
+        return True
+    N, K = (w.shape[0], w.shape[1]) if w_is_nk else (w.shape[1], w.shape[0])
+    if _ops.hip.skinny_gemm_excluded(N, K, w_is_nk):
+        return False
+    from ...ops import fallback
+    fallback.note("decode_gemm", f"{_ops.hip.skinny_gemm_why_not(x2, w, w_is_nk, bias, residual)} -> library GEMM")
+    return False
+
+
+def _skinny_linear(x, w, bias=None, act="none", residual=None):
+    """act(x . w + bias) + residual for x [..., K] of at most 16 rows and w [K, N] on the
+    weight-streaming kernels, or None where _skinny_ok keeps the product on today's path"""
+    x2 = x.reshape(-1, x.shape[-1])
+    r2 = None if residual is None else residual.reshape(-1, residual.shape[-1])
+    if r2 is not None and not r2.is_contiguous():
+        r2 = r2.contiguous()   # e.g. one token sliced out of a [B, T, E] input: at most 16 rows to copy
+    if not _skinny_ok(x2, w, False, bias, r2):
+        return None
+    return _ops.hip.skinny_gemm(x2, w, False, bias, act, r2).reshape(*x.shape[:-1], w.shape[-1])
+
+
 def fused_matmul_bias(x, y, bias=None, transpose_x=False, transpose_y=False, name=None):
     a, b = _u(x), _u(y)
+    if (not transpose_x and a.is_cuda and a.dim() in (2, 3) and b.dim() == 2 and a.shape[-1] > 0
+            and a.numel() // a.shape[-1] <= _ops.hip.SKINNY_GEMM_MAX_M):
+        # at most 16 rows: the weight-streaming kernel reads y in either layout, no transposed copy
+        a2 = a.reshape(-1, a.shape[-1])
+        if _skinny_ok(a2, b, bool(transpose_y), _u(bias)):
+            out = _ops.hip.skinny_gemm(a2, b, bool(transpose_y), _u(bias))
+            return _wrap(out.reshape(*a.shape[:-1], out.shape[-1]))
     if transpose_x:
         a = a.transpose(-1, -2)
     if transpose_y:
@@ -203,7 +251,11 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     decode stage's bias add, cache append and attention are one split-KV kernel pair
     (csrc/kernels/decode_attn.hip); with ``time_step`` an int32 device tensor that step reads it on
     the device, so it neither syncs the host nor changes shape and can be captured in a hipGraph.
-    PHA_DECODE_ATTN=0 keeps the composite."""
+    PHA_DECODE_ATTN=0 keeps the composite. With at most 16 rows (B * S <= 16) and no gradient the four
+    products of each layer run on the weight-streaming kernels (csrc/kernels/skinny_gemm.hip): QKV in
+    either ``trans_qkvw`` layout without a transposed copy, the output projection and ffn2 with bias
+    and residual add in the epilogue (where dropout is an identity and ``ring_id < 0``), ffn1 with bias + GELU / ReLU.
+    PHA_DECODE_GEMM=0 keeps the library GEMMs and the separate elementwise passes."""
     h = _u(x)
     B, S, E = h.shape
     ts = ts_dev = None
@@ -215,19 +267,41 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             ts = int(t.reshape(-1)[0].item()) if isinstance(t, torch.Tensor) else int(t)
     mask = _u(attn_mask)
     decode = cache_kvs is not None and time_step is not None and S == 1
+    # at most 16 rows: the products may run on the weight-streaming kernels (_skinny_ok decides each)
+    skinny = isinstance(h, torch.Tensor) and h.is_cuda and B * S <= _ops.hip.SKINNY_GEMM_MAX_M
+    # bias and residual add go into the epilogue only where nothing stands between them and the product
+    # (dropout an identity: rate 0, or inference in the upscale-in-train mode; no all-reduce)
+    epi = skinny and ring_id < 0 and (dropout_rate == 0 or
+                                      (not training and mode in ("upscale_in_train", "upscale-in-train")))
     for i in range(len(qkv_weights)):
         residual = h
         a = _ln(h, _u(ln_scales[i]), _u(ln_biases[i]), epsilon) if pre_layer_norm else h
         w = _u(qkv_weights[i])
         if trans_qkvw:  # [3, H, D, E]
             _, H, D, _ = w.shape
-            qkv = a.reshape(B * S, E) @ w.reshape(3 * H * D, E).t()
+            w2 = w.reshape(3 * H * D, E)
         else:  # [E, 3, H, D]
             _, _, H, D = w.shape
-            qkv = a.reshape(B * S, E) @ w.reshape(E, 3 * H * D)
+            w2 = w.reshape(E, 3 * H * D)
+        a2 = a.reshape(B * S, E)
         qb = _u(qkv_biases[i]) if qkv_biases is not None and qkv_biases[i] is not None else None
-        if decode and _decode_kernel_ok(qkv.reshape(B, 3, H, D), _u(cache_kvs[i]), mask, ts_dev is not None,
-                                        dropout_rate, training):
+        if skinny and _skinny_ok(a2, w2, trans_qkvw):
+            # nothing here needs a gradient, so a stand-in of the product's shape and dtype picks the
+            # attention path first: the decode kernels add the QKV bias themselves, anywhere else it
+            # goes into this product's epilogue
+            use_decode = decode and _decode_kernel_ok(a2.as_strided((B, 3, H, D), (0, 0, 0, 0)), _u(cache_kvs[i]), mask,
+                                                      ts_dev is not None, dropout_rate, training)
+            qbe = None if use_decode or qb is None else qb.reshape(-1)
+            if qbe is not None and not _ops.hip.skinny_gemm_supported(a2, w2, trans_qkvw, qbe):
+                qbe = None   # added below as today
+            qkv = _ops.hip.skinny_gemm(a2, w2, trans_qkvw, qbe)
+            if qbe is not None:
+                qb = None
+        else:
+            qkv = a2 @ (w2.t() if trans_qkvw else w2)
+            use_decode = decode and _decode_kernel_ok(qkv.reshape(B, 3, H, D), _u(cache_kvs[i]), mask,
+                                                      ts_dev is not None, dropout_rate, training)
+        if use_decode:
             # one split-KV kernel pair: bias add, cache append and attention over [0, time_step]
             if qb is not None and (qb.dtype != qkv.dtype or not qb.is_contiguous()):
                 qb = qb.to(qkv.dtype).contiguous()
@@ -256,19 +330,31 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                 m = m[..., :k.shape[2]]
             o = _attention(q, k, v, m, dropout_rate, training, mode, causal=causal and S > 1)
             o = o.transpose(1, 2).reshape(B, S, H * D)
-        o = _linear(o, _u(linear_weights[i]), _u(linear_biases[i]) if linear_biases is not None else None)
-        if ring_id >= 0:
-            torch.distributed.all_reduce(o)
-        h = residual + _dropout(o, dropout_rate, training, mode)
+        lw, lb = _u(linear_weights[i]), _u(linear_biases[i]) if linear_biases is not None else None
+        o2 = _skinny_linear(o, lw, lb, "none", residual if epi else None) if skinny else None
+        if o2 is not None and epi:
+            h = o2
+        else:
+            o = o2 if o2 is not None else _linear(o, lw, lb)
+            if ring_id >= 0:
+                torch.distributed.all_reduce(o)
+            h = residual + _dropout(o, dropout_rate, training, mode)
         if not pre_layer_norm:
             h = _ln(h, _u(ln_scales[i]), _u(ln_biases[i]), epsilon)
         residual = h
         f = _ln(h, _u(ffn_ln_scales[i]), _u(ffn_ln_biases[i]), epsilon) if pre_layer_norm else h
-        f = _act(f @ _u(ffn1_weights[i]), _u(ffn1_biases[i]) if ffn1_biases is not None else None, activation)
-        f = _linear(f, _u(ffn2_weights[i]), _u(ffn2_biases[i]) if ffn2_biases is not None else None)
-        if ring_id >= 0:
-            torch.distributed.all_reduce(f)
-        h = residual + _dropout(f, dropout_rate, training, mode)
+        w1, b1 = _u(ffn1_weights[i]), _u(ffn1_biases[i]) if ffn1_biases is not None else None
+        f1 = _skinny_linear(f, w1, b1, activation) if skinny and activation in ("gelu", "relu") else None
+        f = f1 if f1 is not None else _act(f @ w1, b1, activation)
+        w2f, b2 = _u(ffn2_weights[i]), _u(ffn2_biases[i]) if ffn2_biases is not None else None
+        f2 = _skinny_linear(f, w2f, b2, "none", residual if epi else None) if skinny else None
+        if f2 is not None and epi:
+            h = f2
+        else:
+            f = f2 if f2 is not None else _linear(f, w2f, b2)
+            if ring_id >= 0:
+                torch.distributed.all_reduce(f)
+            h = residual + _dropout(f, dropout_rate, training, mode)
         if not pre_layer_norm:
             h = _ln(h, _u(ffn_ln_scales[i]), _u(ffn_ln_biases[i]), epsilon)
     if cache_kvs is not None:

@@ -1323,3 +1323,153 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
     _check(L.pha_decode_attn(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc, ts,
                              _ptr(ts_dev), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
     return out
+
+
+# ----------------------------------------------------------------------------
+# weight-streaming GEMM for M <= 16 rows (csrc/kernels/skinny_gemm.hip)
+# ----------------------------------------------------------------------------
+_SKINNY_ACT = {"none": 0, "gelu": 1, "relu": 2}
+
+
+def _skinny_lib():
+    """the kernel library with the skinny-GEMM signatures set, or None where it is not built"""
+    L = _lib.lib
+    if L is None or not hasattr(L, "pha_skinny_gemm"):
+        return None
+    if not getattr(L, "_skinny_gemm_sig", False):
+        P, I, LG = c_void_p, c_int, c_long
+        IP = ctypes.POINTER(c_int)
+        L.pha_skinny_gemm_tile.argtypes = [I, IP, IP]
+        L.pha_skinny_gemm_plan.argtypes = [I, I, I, IP, IP]
+        L.pha_skinny_gemm.argtypes = [I, I, P, LG, P, P, P, P, P, I, I, I, I, I, I, P]
+        for f in (L.pha_skinny_gemm_tile, L.pha_skinny_gemm_plan, L.pha_skinny_gemm):
+            f.restype = c_int
+        L._skinny_gemm_sig = True
+    return L
+
+
+SKINNY_GEMM_MAX_M = 16   # one MFMA 16x16x32 row block
+
+
+def skinny_gemm_tile(w_is_nk):
+    """(column tile, K step per iteration) of the kernel for a weight layout"""
+    L = _skinny_lib()
+    if L is None:
+        raise RuntimeError("libpha_kernels.so not loaded")
+    bn, ks = c_int(0), c_int(0)
+    _check(L.pha_skinny_gemm_tile(1 if w_is_nk else 0, ctypes.byref(bn), ctypes.byref(ks)), "skinny_gemm_tile")
+    return bn.value, ks.value
+
+
+def skinny_gemm_plan(N, K, w_is_nk):
+    """(nsplit, k_per_split) the kernel uses for an [M, K] x [K, N] product: a function of N, K and the
+    weight layout alone (never M or data), so a captured graph stays valid and results reproduce"""
+    L = _skinny_lib()
+    if L is None:
+        raise RuntimeError("libpha_kernels.so not loaded")
+    ns, kps = c_int(0), c_int(0)
+    if int(N) < 1 or int(K) < 1:
+        raise ValueError(f"skinny_gemm_plan: N={N} K={K} must be positive")
+    _check(L.pha_skinny_gemm_plan(int(N), int(K), 1 if w_is_nk else 0, ctypes.byref(ns), ctypes.byref(kps)),
+           "skinny_gemm_plan")
+    return ns.value, kps.value
+
+
+def _skinny_reject(x, w, w_is_nk, bias, residual):
+    """why skinny_gemm cannot take these arguments (names the argument), or None"""
+    if not (isinstance(x, torch.Tensor) and isinstance(w, torch.Tensor)):
+        return "x and w must be tensors"
+    if not x.is_cuda:
+        return f"x is on {x.device}, not a GPU"
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        return f"x is {x.dtype}; the kernel takes bfloat16 or float16"
+    dev, dt = x.device, x.dtype
+    if x.dim() != 2:
+        return f"x must be 2-D, got {tuple(x.shape)}"
+    if w.dim() != 2:
+        return f"w must be 2-D, got {tuple(w.shape)}"
+    M, K = x.shape
+    if M < 1 or M > SKINNY_GEMM_MAX_M:
+        return f"x has M={M} rows; the kernel takes 1 to {SKINNY_GEMM_MAX_M}"
+    N, Kw = (w.shape[0], w.shape[1]) if w_is_nk else (w.shape[1], w.shape[0])
+    if Kw != K:
+        return f"w {tuple(w.shape)} does not match x's K={K} (w_is_nk={bool(w_is_nk)})"
+    if K % 8 or N % 8 or K < 8 or N < 8:
+        return f"K={K} and N={N} must be positive multiples of 8"
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.stride(0) < K:
+        return f"x strides {tuple(x.stride())}: the last must be 1 and the first a multiple of 8 that is >= K"
+    for name, t, shape in (("w", w, tuple(w.shape)), ("bias", bias, (N,)), ("residual", residual, (M, N))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt:
+            return f"{name} must be a {dt} tensor on {dev}"
+        if tuple(t.shape) != shape:
+            return f"{name} must have shape {shape}, got {tuple(t.shape)}"
+        if not t.is_contiguous():
+            return f"{name} is not contiguous"
+    for name, t in (("x", x), ("w", w), ("bias", bias), ("residual", residual)):
+        if t is not None and t.data_ptr() % 16:
+            return f"{name} is not 16-byte aligned"
+    return None
+
+
+def skinny_gemm_supported(x, w, w_is_nk, bias=None, residual=None):
+    """what skinny_gemm takes: bf16 / fp16 tensors of one dtype on one GPU, x [M, K] with 1 <= M <= 16,
+    unit inner stride and a row stride that is a multiple of 8, a contiguous w ([N, K] if ``w_is_nk``
+    else [K, N]), K and N multiples of 8, contiguous bias [N] and residual [M, N], every pointer
+    16-byte aligned; and an (N, K, layout) class that skinny_gemm_excluded does not name"""
+    if _skinny_lib() is None or _skinny_reject(x, w, w_is_nk, bias, residual) is not None:
+        return False
+    N = w.shape[0] if w_is_nk else w.shape[1]
+    return not skinny_gemm_excluded(N, x.shape[1], w_is_nk)
+
+
+def skinny_gemm_excluded(N, K, w_is_nk):
+    """(N, K, layout) classes that lost to the library call plus its elementwise passes in
+    tools/bench_decode_gemm.py part (b) and therefore stay on the library by default (a policy, not a
+    fallback; skinny_gemm itself still takes them). None so far: see profiles/decode_gemm/README.md."""
+    return False
+
+
+def skinny_gemm_why_not(x, w, w_is_nk, bias=None, residual=None):
+    """the reason skinny_gemm would reject these arguments, for the fallback log"""
+    if _skinny_lib() is None:
+        return "kernel library without pha_skinny_gemm"
+    return _skinny_reject(x, w, w_is_nk, bias, residual) or "supported"
+
+
+def skinny_gemm(x, w, w_is_nk, bias=None, act="none", residual=None, nsplit=None, out=None):
+    """out[M, N] = act(x[M, K] @ W + bias) + residual on the weight-streaming kernels, M <= 16, fp32
+    accumulation and one rounding. ``w`` is [N, K] when ``w_is_nk`` else [K, N]; ``act`` is "none",
+    "gelu" (erf) or "relu". ``nsplit`` None takes skinny_gemm_plan's deterministic split; an explicit
+    value splits K evenly (in multiples of 8) and must leave no split empty. ``out``, if given, is a
+    contiguous, 16-byte aligned [M, N] tensor of x's dtype on x's device that receives the result."""
+    fn = "skinny_gemm"
+    why = _skinny_reject(x, w, w_is_nk, bias, residual)
+    if why is not None:
+        raise ValueError(f"{fn}: {why}")
+    if act not in _SKINNY_ACT:
+        raise ValueError(f"{fn}: act must be one of {sorted(_SKINNY_ACT)}, got {act!r}")
+    L = _skinny_lib()
+    if L is None:
+        raise RuntimeError("libpha_kernels.so not loaded")
+    M, K = x.shape
+    N = w.shape[0] if w_is_nk else w.shape[1]
+    if nsplit is None:
+        ns, kps = skinny_gemm_plan(N, K, w_is_nk)
+    else:
+        ns = int(nsplit)
+        if ns < 1:
+            raise ValueError(f"{fn}: nsplit={nsplit} must be at least 1")
+        kps = -(-(-(-K // ns)) // 8) * 8
+        if (ns - 1) * kps >= K:
+            raise ValueError(f"{fn}: nsplit={ns} leaves a split empty at K={K} (k_per_split={kps})")
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != x.dtype or out.device != x.device \
+            or tuple(out.shape) != (M, N) or not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError(f"{fn}: out must be a contiguous, 16-byte aligned {x.dtype} [{M}, {N}] tensor on {x.device}")
+    ws = torch.empty((ns, M, N), dtype=torch.float32, device=x.device) if ns > 1 else None
+    _check(L.pha_skinny_gemm(_DT[x.dtype], 1 if w_is_nk else 0, _ptr(x), x.stride(0), _ptr(w), _ptr(bias),
+                             _ptr(residual), _ptr(out), _ptr(ws), M, N, K, ns, kps, _SKINNY_ACT[act], _stream(x)), fn)
+    return out
