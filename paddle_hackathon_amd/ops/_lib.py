@@ -2,6 +2,8 @@
 
 The library is built in-tree by ``python -m paddle_hackathon_amd.ops.build``
 (or ``__graft_entry__.build()``) into ``paddle_hackathon_amd/_C/libpha_kernels.so``.
+Loading it declares the ctypes signature of every entry point from the one table in
+``_abi.py``; the op modules only call.
 """
 from __future__ import annotations
 
@@ -9,6 +11,8 @@ import ctypes
 import os
 
 import torch
+
+from . import _abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "_C", "libpha_kernels.so")
@@ -27,11 +31,21 @@ def _load():
         _load_error = f"{LIB_PATH} not built (run python -m paddle_hackathon_amd.ops.build)"
         return None
     try:
-        lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    except OSError as e:  # pragma: no cover - depends on ROCm runtime presence
+        L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
+        _abi.declare(L)   # RuntimeError naming the symbol if the table and the library disagree
+    except (OSError, RuntimeError) as e:  # pragma: no cover - depends on ROCm runtime presence
         _load_error = str(e)
-        lib = None
+        return None
+    lib = L
     return lib
+
+
+def loaded():
+    """the kernel library with every signature declared; a missing library is an error"""
+    L = _load()
+    if L is None:
+        raise RuntimeError(f"libpha_kernels.so not loaded: {_load_error}")
+    return L
 
 
 def native_available():

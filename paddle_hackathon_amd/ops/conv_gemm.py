@@ -16,8 +16,7 @@ other shapes use the portable path in nn.functional.conv.
 """
 from __future__ import annotations
 
-import ctypes
-from ctypes import byref, c_int, c_long, c_void_p
+from ctypes import byref, c_int, c_void_p
 
 import json
 import os
@@ -25,30 +24,14 @@ import os
 import torch
 
 from . import _lib
+from ._abi import DT as _DT, ptr as _ptr, stream as _stream
 
 A_ROW, A_COL, A_CONV = 0, 1, 2
 B_ROW, B_COL, B_CONV = 0, 1, 2
 EPI = {None: 0, "relu": 1, "gelu": 2}
-_DT = {torch.bfloat16: 1, torch.float16: 2}
-_sig = False
+_HALF = (torch.bfloat16, torch.float16)   # what the MFMA kernels here take
 _zero = {}
-
-
-def _L():
-    global _sig
-    L = _lib.lib
-    if L is None:
-        raise RuntimeError("libpha_kernels.so not loaded")
-    if not _sig:
-        P, I, LG = c_void_p, c_int, c_long
-        L.pha_gemm.argtypes = [I, I, I, I, P, LG, P, LG, P, LG, P, LG, LG, LG, I, P, P, P, P]
-        L.pha_gemm.restype = c_int
-        _sig = True
-    return L
-
-
-def _ptr(t):
-    return c_void_p(0 if t is None else t.data_ptr())
+_L = _L256 = _lib.loaded   # _L256: the name the gemm256 scripts under tools/ call
 
 
 def _zero_page(dev):
@@ -82,10 +65,9 @@ def gemm_raw(amode, bmode, a, lda, b, ldb, c, ldc, M, N, K, bias=None, act=None,
     ws = torch.empty(sk * M * N, dtype=torch.float32, device=dev) if sk > 1 else None
     cv = None
     if conv is not None:
-        cv = (ctypes.c_int * 14)(*conv)
-    stream = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        cv = (c_int * 14)(*conv)
     rc = _L().pha_gemm(_DT[c.dtype], amode, bmode, EPI[act], _ptr(a), lda, _ptr(b), ldb, _ptr(c), ldc,
-                       _ptr(bias), M, N, K, sk, _ptr(ws), cv, _ptr(_zero_page(dev)), stream)
+                       _ptr(bias), M, N, K, sk, _ptr(ws), cv, _ptr(_zero_page(dev)), _stream(c))
     if rc != 0:
         raise RuntimeError(f"pha_gemm failed (hip error {rc}) M={M} N={N} K={K} modes=({amode},{bmode})")
     return c
@@ -94,7 +76,7 @@ def gemm_raw(amode, bmode, a, lda, b, ldb, c, ldc, M, N, K, bias=None, act=None,
 # ----------------------------------------------------------------------------- dense matmul
 def matmul(a, b, trans_a=False, trans_b=False, bias=None, act=None):
     """2-D bf16/fp16 matmul on the MFMA kernel: op(a) @ op(b) (+bias) (+act)."""
-    assert a.dim() == 2 and b.dim() == 2 and a.dtype == b.dtype and a.dtype in _DT
+    assert a.dim() == 2 and b.dim() == 2 and a.dtype == b.dtype and a.dtype in _HALF
     a, b = a.contiguous(), b.contiguous()
     M, K = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
     Kb, N = (b.shape[1], b.shape[0]) if trans_b else (b.shape[0], b.shape[1])
@@ -113,7 +95,7 @@ def _geo(N, H, W, C, OH, OW, KH, KW, sh, sw, ph, pw, dh, dw):
 
 
 def supported(x, weight, groups):
-    return (x.is_cuda and x.dtype in _DT and weight.dtype == x.dtype and groups == 1 and x.dim() == 4
+    return (x.is_cuda and x.dtype in _HALF and weight.dtype == x.dtype and groups == 1 and x.dim() == 4
             and x.shape[-1] % 8 == 0 and weight.shape[0] % 8 == 0 and _lib.native_available())
 
 
@@ -223,38 +205,12 @@ def conv2d_nhwc(x, weight, bias, stride, padding, dilation):
 _ACT = {None: 0, "relu": 1, "gelu": 2}
 
 
-def _L256():
-    L = _L()
-    if not getattr(L, "_g256_sig", False):
-        P, I, LG = c_void_p, c_int, c_long
-        L.pha_gemm256_nt.argtypes = [I, P, P, P, P, LG, LG, LG, LG, LG, LG, I, P, I, I, P]
-        L.pha_gemm256_nt.restype = c_int
-        L.pha_conv256_fwd.argtypes = [I, P, P, P, P] + [I] * 13 + [I, P, I, I, P, P, P, P, P, P, P, I, P, P]
-        L.pha_gemm8p.argtypes = [I, P, P, P, P, LG, LG, LG, LG, LG, LG, I, I, I, P, I, P, P]
-        L.pha_gemm8p.restype = c_int
-        L.pha_gemm256_tn.argtypes = [I, P, P, P, P, LG, LG, LG, LG, LG, I, I, P, I, I, P]
-        L.pha_gemm256_tn.restype = c_int
-        L.pha_conv256_wgrad.argtypes = [I, P, P, P, P] + [I] * 13 + [I, P, I, I, P]
-        L.pha_conv256_wgrad.restype = c_int
-        L.pha_conv256_fwd.restype = c_int
-        L.pha_conv256_fwd_f32out.argtypes = [I, P, P, P, P] + [I] * 13 + [I, P, I, I, P, P]
-        L.pha_conv256_fwd_f32out.restype = c_int
-        L.pha_conv256_fwd_grouped.argtypes = [I, P, P, P, P] + [I] * 15 + [LG, I, P, I, I, P, P]
-        L.pha_conv256_fwd_grouped.restype = c_int
-        L.pha_conv256_wgrad_grouped.argtypes = [I, P, P, P, P] + [I] * 15 + [P, I, I, P]
-        L.pha_conv256_wgrad_grouped.restype = c_int
-        L.pha_split3_f32.argtypes = [P, P, LG, LG, I, P]
-        L.pha_split3_f32.restype = c_int
-        L._g256_sig = True
-    return L
-
-
 def gemm8p(a, b, a_kouter=False, b_kouter=False, bias=None, act=None, out=None, splits=1):
     """C = op(A) @ op(B) on the 8-phase ping-pong MFMA kernel (gemm8p.hip).
 
     a: [M, K] (a_kouter=False) or [K, M]; b: B^T [N, K] (b_kouter=False) or B [K, N]. Row strides
     come from the tensors (unit inner stride); M, N, K and the strides % 8 == 0."""
-    assert a.dtype in _DT and b.dtype == a.dtype and a.dim() == 2 and b.dim() == 2
+    assert a.dtype in _HALF and b.dtype == a.dtype and a.dim() == 2 and b.dim() == 2
     assert a.stride(1) == 1 and b.stride(1) == 1
     M, Ka = (a.shape[1], a.shape[0]) if a_kouter else (a.shape[0], a.shape[1])
     N, Kb = (b.shape[1], b.shape[0]) if b_kouter else (b.shape[0], b.shape[1])
@@ -267,9 +223,9 @@ def gemm8p(a, b, a_kouter=False, b_kouter=False, bias=None, act=None, out=None, 
     if splits > 1:
         assert c.is_contiguous()
         ws = torch.empty(splits * M * N, dtype=torch.float32, device=a.device)
-    rc = _L256().pha_gemm8p(_DT[a.dtype], _ptr(a), _ptr(b), _ptr(c), _ptr(bias), M, N, Ka, a.stride(0), b.stride(0),
+    rc = _L().pha_gemm8p(_DT[a.dtype], _ptr(a), _ptr(b), _ptr(c), _ptr(bias), M, N, Ka, a.stride(0), b.stride(0),
                             c.stride(0), int(a_kouter), int(b_kouter), _ACT[act], _ptr(_zero_page(a.device)),
-                            int(splits), _ptr(ws), c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
+                            int(splits), _ptr(ws), _stream(a))
     if rc != 0:
         raise RuntimeError(f"pha_gemm8p failed ({rc}) M={M} N={N} K={Ka}")
     return c
@@ -364,7 +320,7 @@ def _autotune(key, run):
 
 def gemm256_nt(a, bt, bias=None, act=None, out=None):
     """C[M, N] = a[M, K] @ bt[N, K]^T (+ bias fp32[N]) (+ relu/gelu). K-contiguous operands."""
-    assert a.dtype in _DT and bt.dtype == a.dtype and a.dim() == 2 and bt.dim() == 2 and a.shape[1] == bt.shape[1]
+    assert a.dtype in _HALF and bt.dtype == a.dtype and a.dim() == 2 and bt.dim() == 2 and a.shape[1] == bt.shape[1]
     assert a.stride(1) == 1 and bt.stride(1) == 1 and a.shape[1] % 8 == 0 and a.stride(0) % 8 == 0 and bt.stride(0) % 8 == 0
     M, K = a.shape
     N = bt.shape[0]
@@ -373,7 +329,7 @@ def gemm256_nt(a, bt, bias=None, act=None, out=None):
     if bias is not None:
         bias = bias.float().contiguous()
         assert bias.numel() == N
-    L, z, st = _L256(), _ptr(_zero_page(a.device)), c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+    L, z, st = _L(), _ptr(_zero_page(a.device)), _stream(a)
 
     def run(tile, bk):
         rc = L.pha_gemm256_nt(_DT[a.dtype], _ptr(a), _ptr(bt), _ptr(c), _ptr(bias), M, N, K, a.stride(0), bt.stride(0),
@@ -398,7 +354,7 @@ def conv256_fwd(x, w_okkc, stride, padding, dilation, bias=None, act=None, out=N
     the call returns the number of rows written (with y in ``out``).
     ``addend``: a tensor shaped like y (not aliasing it) added in the epilogue after the activation
     — a dgrad that also receives the residual branch's gradient (no bn_stats / bn_bwd with it)."""
-    assert x.dtype in _DT and w_okkc.dtype == x.dtype and x.is_contiguous() and w_okkc.is_contiguous()
+    assert x.dtype in _HALF and w_okkc.dtype == x.dtype and x.is_contiguous() and w_okkc.is_contiguous()
     N, H, W, C = x.shape
     Co, KH, KW, Cw = w_okkc.shape
     assert C == Cw and C % 8 == 0
@@ -421,7 +377,7 @@ def conv256_fwd(x, w_okkc, stride, padding, dilation, bias=None, act=None, out=N
         assert y.shape == (N, OH, OW, Co) and y.is_contiguous()
     if bias is not None:
         bias = bias.float().contiguous()
-    L, z, st = _L256(), _ptr(_zero_page(x.device)), c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    L, z, st = _L(), _ptr(_zero_page(x.device)), _stream(x)
     part, rows = None, c_int(0)
     if bn_stats and rm is None and bn_bwd is None:
         part = torch.empty(-(-(N * OH * OW) // 128) * 2 * Co, dtype=torch.float32, device=x.device)
@@ -549,8 +505,8 @@ def split3(t, dim, order="hhl"):
         shape[dim] *= 3
         out = torch.empty(shape, dtype=torch.bfloat16, device=t.device)
         mask = sum(1 << i for i, c in enumerate(order) if c == "l")
-        rc = _L256().pha_split3_f32(_ptr(t), _ptr(out), t.numel() // inner, inner, mask,
-                                     c_void_p(torch.cuda.current_stream(t.device).cuda_stream))
+        rc = _L().pha_split3_f32(_ptr(t), _ptr(out), t.numel() // inner, inner, mask,
+                                     _stream(t))
         if rc == 0:
             return out
     hi = t.to(torch.bfloat16)
@@ -586,7 +542,7 @@ def conv256_fwd_f32(x3, w3, stride, padding, dilation, bias=None, act=None, out=
         assert y.shape == (N, OH, OW, Co) and y.is_contiguous() and y.dtype == torch.float32
     if bias is not None:
         bias = bias.float().contiguous()
-    L, z, st = _L256(), _ptr(_zero_page(x3.device)), c_void_p(torch.cuda.current_stream(x3.device).cuda_stream)
+    L, z, st = _L(), _ptr(_zero_page(x3.device)), _stream(x3)
     rc = L.pha_conv256_fwd_f32out(_DT[x3.dtype], _ptr(x3), _ptr(w3), _ptr(y), _ptr(bias), N, H, W, C, Co, KH, KW,
                                   sh, sw, ph, pw, dh, dw, _ACT[act], z, -1, 0, rm, st)
     if rc != 0:
@@ -684,7 +640,7 @@ def _gfwd(x, w_g, groups, cig, cog, stride, padding, dilation, out=None, remap=N
         OH = (H + 2 * ph - dh * (KH - 1) - 1) // sh + 1
         OW = (W + 2 * pw - dw * (KW - 1) - 1) // sw + 1
         y = out if out is not None else torch.empty((N, OH, OW, groups * cog), dtype=x.dtype, device=x.device)
-    L, z, st = _L256(), _ptr(_zero_page(x.device)), c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    L, z, st = _L(), _ptr(_zero_page(x.device)), _stream(x)
     rc = L.pha_conv256_fwd_grouped(_DT[x.dtype], _ptr(x), _ptr(w_g), _ptr(y), _ptr(bias), N, H, W, cig, cog, groups,
                                    KH, KW, sh, sw, ph, pw, dh, dw, _ACT[None], y.shape[-1], 0, z, -1, 0, rm, st)
     if rc != 0:
@@ -789,7 +745,7 @@ def _gwgrad(dy, x, w_shape, stride, padding, dilation, groups):
     M, Nn, K = cog, KH * KW * cig, N * OH * OW
     sp = max(1, min(32, K // 32 // 8, -(-2 * _num_cus(dy.device) // max(1, groups * -(-M // 128) * -(-Nn // 128)))))
     ws = torch.empty(groups * sp * M * Nn, dtype=torch.float32, device=dy.device)
-    L, z, st = _L256(), _ptr(_zero_page(x.device)), c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    L, z, st = _L(), _ptr(_zero_page(x.device)), _stream(x)
     rc = L.pha_conv256_wgrad_grouped(_DT[dy.dtype], _ptr(dy), _ptr(x), _ptr(out), _ptr(ws), N, H, W, cig, cog, groups,
                                      KH, KW, sh, sw, ph, pw, dh, dw, 0, z, -1, sp, st)
     if rc != 0:
@@ -929,7 +885,7 @@ def gemm256_tn(a, b, out=None, out_dtype=None, accumulate=False):
     """C[M, N] = a[K, M]^T @ b[K, N] — the weight-gradient product (X^T dY) with both operands
     K-outer as they come out of the forward; fp32 split-K partials, result in ``out_dtype``
     (default a.dtype; torch.float32 for master-weight gradients) or added into ``out``."""
-    assert a.dtype in _DT and b.dtype == a.dtype and a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0]
+    assert a.dtype in _HALF and b.dtype == a.dtype and a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0]
     assert a.stride(1) == 1 and b.stride(1) == 1
     K, M = a.shape
     N = b.shape[1]
@@ -938,7 +894,7 @@ def gemm256_tn(a, b, out=None, out_dtype=None, accumulate=False):
         out = torch.empty(M, N, dtype=od, device=a.device)
         accumulate = False
     assert out.shape == (M, N) and out.is_contiguous() and od in (a.dtype, torch.float32)
-    L, z, st = _L256(), _ptr(_zero_page(a.device)), c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+    L, z, st = _L(), _ptr(_zero_page(a.device)), _stream(a)
 
     tgt = {"out": out, "acc": int(accumulate)}
 
@@ -969,7 +925,7 @@ def conv256_wgrad(dy, x, w_shape, stride, padding, dilation, out_dtype=None):
     od = out_dtype or dy.dtype
     out = torch.empty(Co, Ci, KH, KW, dtype=od, device=dy.device)
     M, Nn, K = Co, KH * KW * Ci, N * OH * OW
-    L, z, st = _L256(), _ptr(_zero_page(x.device)), c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    L, z, st = _L(), _ptr(_zero_page(x.device)), _stream(x)
 
     def call(tile, splits, ws):
         rc = L.pha_conv256_wgrad(_DT[dy.dtype], _ptr(dy), _ptr(x), _ptr(out), _ptr(ws), N, H, W, C, Co, KH, KW,
@@ -1003,7 +959,7 @@ def res_route_begin(x, kind="bn"):
     ``res_route_end`` after the block's forward."""
     import os
     if os.environ.get("PHA_RES_ROUTE", "1") == "0" or not torch.is_grad_enabled() or not x.requires_grad \
-            or not x.is_cuda or x.dtype not in _DT or x.dim() != 4:
+            or not x.is_cuda or x.dtype not in _HALF or x.dim() != 4:
         return None
     if kind == "conv" and os.environ.get("PHA_RES_ROUTE_CONV", "1") == "0":
         return None
@@ -1223,7 +1179,7 @@ def weight_t(w):
     15-35 % faster than NN at the GPT shapes (tools/bench_gpt_gemms.py). The first stale copy met
     after an optimizer step refreshes EVERY stale cached copy on that device in one batched
     transpose launch, in place (pha_transpose16_batch; PHA_WT_BATCH=0: one launch per weight)."""
-    if _WT_BATCH and _tr16_ok(w) and hasattr(_L(), "pha_transpose16_batch"):
+    if _WT_BATCH and _tr16_ok(w):
         return _weight_t_batched(w)
     return _wlayout(w, "t", _transpose2d)
 
@@ -1256,12 +1212,7 @@ def _weight_t_batched(w):
     if not any(k == key for _, _, k in todo):
         _wlayouts.pop(key, None)
         todo.append((w, torch.empty(w.shape[1], w.shape[0], dtype=w.dtype, device=w.device), key))
-    L = _L()
-    if not getattr(L, "_trb_sig", False):
-        L.pha_transpose16_batch.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.pha_transpose16_batch.restype = c_int
-        L._trb_sig = True
-    st = c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
+    L, st = _L(), _stream(w)
     for i in range(0, len(todo), 64):
         chunk = todo[i:i + 64]
         n = len(chunk)
@@ -1287,12 +1238,7 @@ def _transpose2d(t):
     if t.dtype not in (torch.bfloat16, torch.float16) or R % 8 or C % 8 or not t.is_contiguous() or not t.is_cuda:
         return t.t().contiguous()
     out = torch.empty(C, R, dtype=t.dtype, device=t.device)
-    L = _L()
-    if not getattr(L, "_tr_sig", False):
-        L.pha_transpose16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p]
-        L.pha_transpose16.restype = c_int
-        L._tr_sig = True
-    rc = L.pha_transpose16(_ptr(t), _ptr(out), R, C, c_void_p(torch.cuda.current_stream(t.device).cuda_stream))
+    rc = _L().pha_transpose16(_ptr(t), _ptr(out), R, C, _stream(t))
     if rc != 0:
         raise RuntimeError(f"pha_transpose16 failed ({rc})")
     return out

@@ -18,11 +18,11 @@ tokens, a batch of 8) stay on the own kernels.
 from __future__ import annotations
 
 import os
-from ctypes import c_int, c_long, c_void_p
 
 import torch
 
 from . import _lib
+from ._abi import DT as _DT, ptr as _ptr, stream as _stream
 
 EPI_BIAS, EPI_GELU, EPI_RELU, EPI_DGELU, EPI_COLSUM, EPI_AUXOUT, EPI_TRANS = 1, 2, 4, 8, 16, 32, 64
 EPI_RSTAGE = 32768   # gemm4p NT: register-staged operands
@@ -34,36 +34,7 @@ G4P_GELU_DAUX = 4    # gemm4p NT bias + GELU: aux <- gelu_tanh'(acc + bias) inst
 G4P_MULAUX = 8       # gemm4p NT: C = acc * aux (aux an input shaped like C)
 G4P_COLSUM = 1 << 27  # gemm4p TN + EARLY: column sums of B (bias gradient) from the MFMA B fragments
 G4P_SPREAD_SHIFT = 28  # gemm4p NT + EARLY, bits 28-29: LDS-DMA placement over 24-28 MFMA groups
-_DT = {torch.bfloat16: 1, torch.float16: 2, torch.float32: 0}
-
-
-def _L():
-    L = _lib._load()
-    if L is None:
-        raise RuntimeError(f"libpha_kernels.so not loaded: {_lib._load_error}")
-    if not getattr(L, "_g4w_sig", False):
-        P, I, LG = c_void_p, c_int, c_long
-        L.pha_gemm4w.argtypes = [I, P, P, P, LG, LG, LG, LG, LG, LG, I, I, I, P, P, LG, P, I, P]
-        L.pha_gemm4w.restype = c_int
-        L.pha_gemm4p.argtypes = [I, P, P, P, LG, LG, LG, LG, LG, LG, I, I, I, I, P, I, I, P, I, P, P]
-        L.pha_gemm4p.restype = c_int
-        L.pha_gemm4p_batched.argtypes = [I, P, P, P, LG, LG, LG, LG, LG, LG, I, I, I, I, P, I, I, P, I, P, P, I,
-                                         LG, LG, LG]
-        L.pha_gemm4p_batched.restype = c_int
-        L.pha_gemm8w.argtypes = [I, P, P, P, LG, LG, LG, LG, LG, LG, I, P, I, P]
-        L.pha_gemm8w.restype = c_int
-        L.pha_colsum_finish.argtypes = [I, P, P, I, I, P]
-        L.pha_colsum_finish.restype = c_int
-        L._g4w_sig = True
-    return L
-
-
-def _ptr(t):
-    return c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(t):
-    return c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+_L = _lib.loaded
 
 
 def sched_variant(a_kouter=False, b_kouter=False):

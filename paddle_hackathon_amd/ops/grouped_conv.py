@@ -10,46 +10,12 @@ Weights keep Paddle's [C_out, C_in / groups, KH, KW]; the forward re-lays them o
 """
 from __future__ import annotations
 
-from ctypes import c_int, c_long, c_void_p
-
 import torch
 
 from . import _lib
+from ._abi import DT as _DT, check as _check, ptr as _p, stream as _stream
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
-
-def _L():
-    L = _lib._load()
-    if L is None:
-        raise RuntimeError(f"libpha_kernels.so not loaded: {_lib._load_error}")
-    if not getattr(L, "_gconv_sig", False):
-        P = c_void_p
-        L.pha_gconv_fwd.argtypes = [c_int, P, P, P, P, P, P]
-        L.pha_gconv_fwd.restype = c_int
-        L.pha_gconv_dgrad.argtypes = [c_int, P, P, P, P, P]
-        L.pha_gconv_dgrad.restype = c_int
-        L.pha_gconv_wgrad_ws.argtypes = [P, c_int]
-        L.pha_gconv_wgrad_ws.restype = c_long
-        L.pha_gconv_wgrad_items.argtypes = [P]
-        L.pha_gconv_wgrad_items.restype = c_long
-        L.pha_gconv_wgrad.argtypes = [c_int, P, P, P, P, P, c_int, P]
-        L.pha_gconv_wgrad.restype = c_int
-        L._gconv_sig = True
-    return L
-
-
-def _p(t):
-    return c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(t):
-    return c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"pha_gconv_{what} failed ({rc})")
+_L = _lib.loaded
 
 
 def out_size(size, k, s, p, d):
@@ -81,7 +47,7 @@ class GroupedConv2dNHWC(torch.autograd.Function):
         wr = w.permute(2, 3, 1, 0).contiguous()
         y = torch.empty(oshape, dtype=x.dtype, device=x.device)
         b = None if bias is None else bias.float().contiguous()
-        _check(_L().pha_gconv_fwd(_DT[x.dtype], _p(dims), _p(x), _p(wr), _p(b), _p(y), _stream(x)), "fwd")
+        _check(_L().pha_gconv_fwd(_DT[x.dtype], _p(dims), _p(x), _p(wr), _p(b), _p(y), _stream(x)), "pha_gconv_fwd")
         ctx.save_for_backward(x, w)
         ctx.conf = (stride, pad, dil, groups, bias is not None)
         ctx.dims = dims
@@ -99,7 +65,7 @@ class GroupedConv2dNHWC(torch.autograd.Function):
             depthwise = w.shape[1] == 1 and w.shape[0] == groups
             w2 = w.permute(2, 3, 1, 0).contiguous() if depthwise else w.permute(2, 3, 0, 1).contiguous()
             dx = torch.empty_like(x)
-            _check(L.pha_gconv_dgrad(_DT[x.dtype], _p(dims), _p(gy), _p(w2), _p(dx), _stream(x)), "dgrad")
+            _check(L.pha_gconv_dgrad(_DT[x.dtype], _p(dims), _p(gy), _p(w2), _p(dx), _stream(x)), "pha_gconv_dgrad")
         if ctx.needs_input_grad[1]:
             base = L.pha_gconv_wgrad_items(_p(dims))
             npix = gy.shape[0] * gy.shape[1] * gy.shape[2]
@@ -107,7 +73,7 @@ class GroupedConv2dNHWC(torch.autograd.Function):
             ws = torch.empty(L.pha_gconv_wgrad_ws(_p(dims), chunks), dtype=torch.float32, device=x.device)
             dw = torch.empty_like(w)
             _check(L.pha_gconv_wgrad(_DT[x.dtype], _p(dims), _p(x), _p(gy), _p(dw), _p(ws), chunks, _stream(x)),
-                   "wgrad")
+                   "pha_gconv_wgrad")
         if has_b and ctx.needs_input_grad[2]:
             g2 = gy.reshape(-1, gy.shape[-1])
             if gy.dtype in (torch.bfloat16, torch.float16) and g2.shape[1] % 8 == 0:
@@ -135,7 +101,7 @@ class GroupedConvTranspose2dNHWC(torch.autograd.Function):
         depthwise = w.shape[1] == 1 and w.shape[0] == groups
         w2 = w.permute(2, 3, 1, 0).contiguous() if depthwise else w.permute(2, 3, 0, 1).contiguous()
         y = torch.empty(N, OH, OW, Cout, dtype=x.dtype, device=x.device)
-        _check(_L().pha_gconv_dgrad(_DT[x.dtype], _p(dims), _p(x), _p(w2), _p(y), _stream(x)), "dgrad")
+        _check(_L().pha_gconv_dgrad(_DT[x.dtype], _p(dims), _p(x), _p(w2), _p(y), _stream(x)), "pha_gconv_dgrad")
         if bias is not None:
             y += bias.to(y.dtype)
         ctx.save_for_backward(x, w)
@@ -152,7 +118,7 @@ class GroupedConvTranspose2dNHWC(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wr = w.permute(2, 3, 1, 0).contiguous()
             dx = torch.empty_like(x)
-            _check(L.pha_gconv_fwd(_DT[x.dtype], _p(dims), _p(gy), _p(wr), None, _p(dx), _stream(x)), "fwd")
+            _check(L.pha_gconv_fwd(_DT[x.dtype], _p(dims), _p(gy), _p(wr), None, _p(dx), _stream(x)), "pha_gconv_fwd")
         if ctx.needs_input_grad[1]:
             base = L.pha_gconv_wgrad_items(_p(dims))
             npix = x.shape[0] * x.shape[1] * x.shape[2]
@@ -160,7 +126,7 @@ class GroupedConvTranspose2dNHWC(torch.autograd.Function):
             ws = torch.empty(L.pha_gconv_wgrad_ws(_p(dims), chunks), dtype=torch.float32, device=x.device)
             dw = torch.empty_like(w)
             _check(L.pha_gconv_wgrad(_DT[x.dtype], _p(dims), _p(gy), _p(x), _p(dw), _p(ws), chunks, _stream(x)),
-                   "wgrad")
+                   "pha_gconv_wgrad")
         if ctx.has_b and ctx.needs_input_grad[2]:
             db = gy.reshape(-1, gy.shape[-1]).float().sum(0).to(gy.dtype)
         return dx, dw, db, None, None, None, None, None

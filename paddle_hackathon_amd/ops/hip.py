@@ -3,86 +3,22 @@
 Each call passes raw device pointers and the *current* torch HIP stream, so the
 kernels order correctly with PyTorch-ROCm's own work and are capturable in HIP
 graphs. Shape preconditions are checked here on the host before any launch
-(a kernel reading out of bounds can take the whole GPU node down).
+(a kernel reading out of bounds can take the whole GPU node down). The argument types of
+every entry point are declared once, in ``_abi.SIGNATURES``, when ``_lib`` loads the library:
+call sites here pass plain Python numbers and the ``_ptr`` / ``_stream`` addresses.
 """
 from __future__ import annotations
 
 import ctypes
-from ctypes import c_uint, c_int, c_long, c_float, c_void_p
+from ctypes import c_int
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._abi import DT as _DT, check as _check, ptr as _ptr, stream as _stream
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-_sigs_done = False
-
-
-def _L():
-    global _sigs_done
-    L = _lib.lib
-    if L is None:
-        raise RuntimeError("libpha_kernels.so not loaded")
-    if not _sigs_done:
-        P, I, F, LG = c_void_p, c_int, c_float, c_long
-        sig = {
-            "pha_layer_norm_fwd": [I, I, P, P, P, P, P, P, I, I, F, P],
-            "pha_layer_norm_bwd": [I, I, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
-            "pha_layer_norm_bwd_nblocks": [I, I],
-            "pha_layer_norm_fwd2": [I, I, P, P, P, P, P, P, P, P, I, I, F, P],
-            "pha_layer_norm_bwd2": [I, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
-            "pha_layer_norm_bwd3": [I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
-            "pha_bdrln_fwd2": [I, I, I, P, P, P, P, P, P, P, P, P, I, I, F, c_uint, c_uint, F, P, P],
-            "pha_col_sum_rows": [I, P, P, I, I, P],
-            "pha_bdrln_fwd": [I, I, P, P, P, P, P, P, P, P, P, I, I, F, c_uint, c_uint, F, P],
-            "pha_dropout_bias_bwd": [I, I, P, P, P, P, I, I, I, c_uint, c_uint, F, P, P],
-            "pha_layer_norm_dropout_bwd": [I, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, c_uint, c_uint, F, P, P],
-            "pha_softmax_fwd": [I, P, P, I, I, P],
-            "pha_softmax_bwd": [I, P, P, P, I, I, P],
-            "pha_softmax_ce_fwd": [I, P, P, P, P, LG, I, I, P],
-            "pha_softmax_ce_bwd": [I, P, P, P, P, P, LG, I, I, P],
-            "pha_bias_gelu_fwd": [I, P, P, P, LG, I, I, P],
-            "pha_bias_gelu_bwd": [I, P, P, P, P, LG, I, I, P],
-            "pha_embedding_fwd": [P, P, P, LG, I, LG, P],
-            "pha_embedding_bwd": [I, P, P, P, LG, I, LG, LG, P, I, P],
-            "pha_multi_tensor_adam": [I, I, P, P, I, F, F, F, F, F, F, F, I, P, P, P, P, P],
-            "pha_multi_tensor_momentum": [I, I, P, P, I, F, F, F, I, P],
-            "pha_multi_tensor_l2sq": [P, P, I, P, P, P],
-            "pha_lamb_sq": [P, LG, P, P, P],
-            "pha_lamb_moment": [P, P, P, P, P, P, P, I, LG, F, F, F, F, F, F, F, P, P],
-            "pha_lamb_apply": [P, P, P, P, P, I, LG, F, P, P],
-            "pha_bn_num_blocks": [LG, I],
-            "pha_bn_fwd_train": [I, P, P, P, LG, I, P, P, P, P, P, P, P, P, P, F, F, I, P, I, P],
-            "pha_bn_apply": [I, P, P, P, LG, I, P, P, I, P],
-            "pha_bn_bwd": [I, P, P, P, LG, I, P, P, P, P, P, P, P, P, P, I, P, P, I, P],
-            "pha_chunk_size": [],
-            "pha_tensor_meta_size": [],
-        }
-        for name, args in sig.items():
-            f = getattr(L, name, None)
-            if f is None:
-                continue
-            f.argtypes = args
-            f.restype = c_int
-        for name in ("pha_flash_attn_fwd", "pha_flash_attn_bwd", "pha_flash_attn_bwd_preprocess"):
-            if hasattr(L, name):
-                getattr(L, name).restype = c_int
-        _sigs_done = True
-    return L
-
-
-def _stream(t):
-    return c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _ptr(t):
-    return None if t is None else c_void_p(t.data_ptr())
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with hipError {rc}")
+_L = _lib.loaded
 
 
 # ----------------------------------------------------------------------------
@@ -148,14 +84,9 @@ def dropout_seed(device):
     if not torch.cuda.is_current_stream_capturing():
         return seed, None
     out = torch.empty(1, dtype=torch.int32, device=device)
-    L = _L()
-    if hasattr(L, "pha_seed_bump"):   # ++counter and the site's copy in one captured kernel
-        L.pha_seed_bump.argtypes = [c_void_p, c_void_p, c_void_p]
-        L.pha_seed_bump.restype = c_int
-        _check(L.pha_seed_bump(_ptr(buf), _ptr(out), _stream(buf)), "seed_bump")
-        return seed, out
-    buf.add_(1)
-    return seed, buf.clone()
+    # ++counter and the site's copy in one captured kernel
+    _check(_L().pha_seed_bump(_ptr(buf), _ptr(out), _stream(buf)), "seed_bump")
+    return seed, out
 
 
 _SEED_BUFS = {}
@@ -346,22 +277,18 @@ def bias_gelu_bwd(gy, x, b, approximate, want_db=True):
         gx = torch.empty_like(x)
         rows = n // H
         rpb = max(16, -(-rows // 512))
-        L = _L()
-        L.pha_bias_gelu_bwd_rows.restype = c_int
-        _check(L.pha_bias_gelu_bwd_rows(_DT[x.dtype], _ptr(gy), _ptr(x), _ptr(b), _ptr(gx), c_int(rows), c_int(H),
-                                        c_int(rpb), c_int(int(approximate)), _stream(x)), "bias_gelu_bwd_rows")
+        _check(_L().pha_bias_gelu_bwd_rows(_DT[x.dtype], _ptr(gy), _ptr(x), _ptr(b), _ptr(gx), rows, H, rpb,
+                                           int(approximate), _stream(x)), "bias_gelu_bwd_rows")
         return gx, None
-    elif b is not None and want_db and x.dtype != torch.float32 and hasattr(_L(), "pha_bias_gelu_bwd_db"):
+    elif b is not None and want_db and x.dtype != torch.float32:
         # gx and the per-row-block column sums of gx in one pass; db = sum of the partials
         gx = torch.empty_like(x)
         rows = n // H
         rpb = max(16, -(-rows // 512))   # >= 2048 blocks at 16384 x 8192: 8 per CU for streaming
         P = -(-rows // rpb)
         part = torch.empty((P + 8, H), dtype=torch.float32, device=x.device)   # + column-sum stage rows
-        L = _L()
-        L.pha_bias_gelu_bwd_db.restype = c_int
-        _check(L.pha_bias_gelu_bwd_db(_DT[x.dtype], _ptr(gy), _ptr(x), _ptr(b), _ptr(gx), _ptr(part), c_int(rows),
-                                      c_int(H), c_int(rpb), c_int(int(approximate)), _stream(x)), "bias_gelu_bwd_db")
+        _check(_L().pha_bias_gelu_bwd_db(_DT[x.dtype], _ptr(gy), _ptr(x), _ptr(b), _ptr(gx), _ptr(part), rows, H, rpb,
+                                         int(approximate), _stream(x)), "bias_gelu_bwd_db")
         return gx, _col_sum_rows(part, P, b.dtype)
     else:
         gx = torch.empty_like(x)
@@ -379,10 +306,8 @@ def col_sum(gy2d, out_dtype=None):
     rpb = max(16, -(-rows // 512))
     P = -(-rows // rpb)
     part = torch.empty((P + 8, H), dtype=torch.float32, device=gy2d.device)   # + column-sum stage rows
-    L = _L()
-    L.pha_col_sum_partial.restype = c_int
-    _check(L.pha_col_sum_partial(_DT[gy2d.dtype], _ptr(gy2d), _ptr(part), c_int(rows), c_int(H), c_int(rpb),
-                                 _stream(gy2d)), "col_sum_partial")
+    _check(_L().pha_col_sum_partial(_DT[gy2d.dtype], _ptr(gy2d), _ptr(part), rows, H, rpb, _stream(gy2d)),
+           "col_sum_partial")
     return _col_sum_rows(part, P, out_dtype or gy2d.dtype)
 
 
@@ -390,7 +315,7 @@ def _col_sum_rows(part, P, dtype):
     """column sums of the first P rows of the fp32 partials ``part`` ([P + 8, H]: the last rows are
     the kernel's first-stage workspace) into a new [H] tensor of ``dtype``"""
     H = part.shape[1]
-    if dtype not in _DT or not hasattr(_L(), "pha_col_sum_rows"):
+    if dtype not in _DT:
         return part[:P].sum(0).to(dtype)
     out = torch.empty(H, dtype=dtype, device=part.device)
     _check(_L().pha_col_sum_rows(_DT[dtype], _ptr(part), _ptr(out), P, H, _stream(part)), "col_sum_rows")
@@ -408,10 +333,8 @@ class MaxPool2dNHWC(torch.autograd.Function):
         OW = (W + 2 * p[1] - k[1]) // s[1] + 1
         y = torch.empty(N, OH, OW, C, dtype=x.dtype, device=x.device)
         idx = torch.empty(N, OH, OW, C, dtype=torch.uint8, device=x.device)
-        L = _L()
-        L.pha_maxpool2d_nhwc_fwd.restype = c_int
-        _check(L.pha_maxpool2d_nhwc_fwd(_DT[x.dtype], _ptr(x), _ptr(y), _ptr(idx), *[c_int(v) for v in (
-            N, H, W, C, OH, OW, k[0], k[1], s[0], s[1], p[0], p[1])], _stream(x)), "maxpool2d_nhwc_fwd")
+        _check(_L().pha_maxpool2d_nhwc_fwd(_DT[x.dtype], _ptr(x), _ptr(y), _ptr(idx), N, H, W, C, OH, OW,
+                                           k[0], k[1], s[0], s[1], p[0], p[1], _stream(x)), "maxpool2d_nhwc_fwd")
         ctx.save_for_backward(idx)
         ctx.conf = (x.shape, k, s, p)
         return y
@@ -422,17 +345,15 @@ class MaxPool2dNHWC(torch.autograd.Function):
         (N, H, W, C), k, s, p = ctx.conf
         gy = gy.contiguous()
         gx = torch.empty(N, H, W, C, dtype=gy.dtype, device=gy.device)
-        L = _L()
-        L.pha_maxpool2d_nhwc_bwd.restype = c_int
-        _check(L.pha_maxpool2d_nhwc_bwd(_DT[gy.dtype], _ptr(gy), _ptr(idx), _ptr(gx), *[c_int(v) for v in (
-            N, H, W, C, idx.shape[1], idx.shape[2], k[0], k[1], s[0], s[1], p[0], p[1])], _stream(gy)),
+        _check(_L().pha_maxpool2d_nhwc_bwd(_DT[gy.dtype], _ptr(gy), _ptr(idx), _ptr(gx), N, H, W, C, idx.shape[1],
+                                           idx.shape[2], k[0], k[1], s[0], s[1], p[0], p[1], _stream(gy)),
                "maxpool2d_nhwc_bwd")
         return gx, None, None, None
 
 
 def maxpool_nhwc_ok(x, k, s, p):
     return (x.is_cuda and x.dim() == 4 and x.dtype in _DT and x.shape[-1] % 8 == 0 and x.is_contiguous()
-            and k[0] * k[1] <= 256 and p[0] < k[0] and p[1] < k[1] and hasattr(_L(), "pha_maxpool2d_nhwc_fwd"))
+            and k[0] * k[1] <= 256 and p[0] < k[0] and p[1] < k[1])
 
 
 def embedding_fwd(ids, w):
@@ -787,8 +708,7 @@ def flash_attn_supported(q, k, v, dropout_p, mask=None):
     import os
     if os.environ.get("PHA_DISABLE_FLASH") == "1":
         return False
-    L = _lib.lib
-    if L is None or not hasattr(L, "pha_flash_attn_fwd"):
+    if _lib.lib is None:
         return False
     if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
         return False
@@ -842,9 +762,8 @@ def _fa64_on(D, mask, Sk=None):
     dropout whose keep bits the forward stores for the backward, an additive mask read as float4 key
     quads: Sk % 4 == 0); PHA_FA64=0 keeps the generic 4-wave kernels"""
     import os
-    L = _lib.lib
-    return (D == 64 and (mask is None or (Sk is not None and Sk % 4 == 0)) and L is not None
-            and hasattr(L, "pha_fa64_fwd") and os.environ.get("PHA_FA64", "1") != "0")
+    return (D == 64 and (mask is None or (Sk is not None and Sk % 4 == 0)) and _lib.lib is not None
+            and os.environ.get("PHA_FA64", "1") != "0")
 
 
 def _fa64_bias(mask, B, H, S, Sk, device):
@@ -858,30 +777,13 @@ def _fa64_bias(mask, B, H, S, Sk, device):
     return bias, st
 
 
-def _fa64_sig(L):
-    if not getattr(L, "_fa64_sig", False):
-        P, I, LG, F, U = c_void_p, c_int, c_long, c_float, ctypes.c_uint
-        L.pha_fa64_fwd.argtypes = [I, P, P, P, P, P, I, I, I, I, I, F, I, LG, I, LG, I, LG, I, F, U, P, P, P,
-                                   P, LG, LG, LG]
-        L.pha_fa64_fwd.restype = c_int
-        L.pha_fa64_bwd.argtypes = [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, LG, I, LG, I, LG, I, LG, I,
-                                   LG, I, F, U, P, P, P, P, LG, LG, LG]
-        L.pha_fa64_mask_words.argtypes = [I]
-        L.pha_fa64_mask_words.restype = c_int
-        L.pha_fa64_mask_size.argtypes = [I, I, I, I]
-        L.pha_fa64_mask_size.restype = c_long
-        L.pha_fa64_bwd.restype = c_int
-        L._fa64_sig = True
-    return L
-
-
 def _fa64_fwd(dt, qp, kp, vp, o, lse, B, S, Sk, H, Hk, sc, causal, qs, kvs, os_, dropout_p, seed, seed_dev, st,
               bias=None, bst=(0, 0, 0)):
     """qs / kvs / os_: (token, head) element strides of q, k / v and o. With dropout, returns the keep
     mask as bits (int32 [B * H][words][S up to 64]) for the backward — the reference fused attention keeps
     its dropout mask too (fmha_ref.h dropout_mask_out); PHA_FA64_MASKBITS=0 re-hashes instead"""
     import os
-    L = _fa64_sig(_L())
+    L = _L()
     dmask = None
     if dropout_p and os.environ.get("PHA_FA64_MASKBITS", "1") != "0":
         dmask = torch.empty(L.pha_fa64_mask_size(B, H, S, Sk), dtype=torch.int32, device=o.device)
@@ -894,7 +796,7 @@ def _fa64_fwd(dt, qp, kp, vp, o, lse, B, S, Sk, H, Hk, sc, causal, qs, kvs, os_,
 
 def _fa64_bwd(dt, qp, kp, vp, do, lse, delta, dqp, dkp, dvp, B, S, Sk, H, Hk, sc, causal, qs, kvs, gqs, gkvs,
               dropout_p, seed, seed_dev, st, dmask=None, bias=None, bst=(0, 0, 0)):
-    L = _fa64_sig(_L())
+    L = _L()
     _check(L.pha_fa64_bwd(dt, qp, kp, vp, _ptr(do), _ptr(lse), _ptr(delta), dqp, dkp, dvp, B, S, Sk, H, Hk, sc,
                           int(causal), qs[0], qs[1], kvs[0], kvs[1], H * 64, 64, gqs[0], gqs[1], gkvs[0], gkvs[1],
                           float(dropout_p), seed, _ptr(seed_dev), st, _ptr(dmask), _ptr(bias), bst[0], bst[1],
@@ -926,19 +828,9 @@ class FlashAttentionExt(torch.autograd.Function):
             ctx.bias, ctx.strides, ctx.seed, ctx.seed_dev = b64, bst, seed, seed_dev
             ctx.causal, ctx.scale, ctx.dropout_p = causal, sc, float(dropout_p)
             return o
-        L = _L()
-        if not getattr(L, "_fa_ext_sig", False):
-            P, I, LG, F, U = c_void_p, c_int, c_long, c_float, ctypes.c_uint
-            L.pha_flash_attn_fwd_ext.argtypes = [I, P, P, P, P, P, I, I, I, I, I, I, F, I, P, LG, LG, LG, F, U, P, P]
-            L.pha_flash_attn_fwd_ext.restype = c_int
-            L.pha_flash_attn_bwd_ext.argtypes = [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P, LG, LG, LG,
-                                                 F, U, P, LG, I, LG, I, P]
-            L.pha_flash_attn_bwd_ext.restype = c_int
-            L._fa_ext_sig = True
-        _check(L.pha_flash_attn_fwd_ext(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), B, S, Sk, H, Hk, D,
-                                        sc, int(causal), _ptr(bias), sb, sh, sq, float(dropout_p), seed, _stream(q),
-                                        _ptr(seed_dev)),
-               "flash_attn_fwd_ext")
+        _check(_L().pha_flash_attn_fwd_ext(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), B, S, Sk, H, Hk,
+                                           D, sc, int(causal), _ptr(bias), sb, sh, sq, float(dropout_p), seed,
+                                           _stream(q), _ptr(seed_dev)), "flash_attn_fwd_ext")
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.bias, ctx.strides, ctx.seed, ctx.seed_dev = bias, (sb, sh, sq), seed, seed_dev
         ctx.causal, ctx.scale, ctx.dropout_p = causal, sc, float(dropout_p)
@@ -955,8 +847,8 @@ class FlashAttentionExt(torch.autograd.Function):
         dq = torch.empty_like(q)
         dk = torch.empty_like(k) if Hk == H else torch.empty((B, Sk, H, D), dtype=k.dtype, device=k.device)
         dv = torch.empty_like(v) if Hk == H else torch.empty((B, Sk, H, D), dtype=v.dtype, device=v.device)
-        _check(L.pha_flash_attn_bwd_preprocess(c_int(_DT[q.dtype]), _ptr(o), _ptr(do), _ptr(delta), c_int(B), c_int(S),
-                                               c_int(H), c_int(D), _stream(q)), "flash_attn_bwd_preprocess")
+        _check(L.pha_flash_attn_bwd_preprocess(_DT[q.dtype], _ptr(o), _ptr(do), _ptr(delta), B, S, H, D, _stream(q)),
+               "flash_attn_bwd_preprocess")
         if getattr(ctx, "fa64", False):
             _fa64_bwd(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), do, lse, delta, _ptr(dq), _ptr(dk), _ptr(dv), B, S, Sk,
                       H, Hk, ctx.scale, ctx.causal, (H * D, D), (Hk * D, D), (0, 0), (0, 0), ctx.dropout_p, ctx.seed,
@@ -993,9 +885,9 @@ class FlashAttentionExtPacked(torch.autograd.Function):
             lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
             es, base = qkv.element_size(), qkv.data_ptr()
             b64, bst = _fa64_bias(mask, B, H, S, S, qkv.device)
-            ctx.dmask = _fa64_fwd(_DT[qkv.dtype], c_void_p(base), c_void_p(base + D * es),
-                                  c_void_p(base + 2 * D * es), o, lse, B, S, S, H, H, sc, causal, (3 * H * D, 3 * D),
-                                  (3 * H * D, 3 * D), (H * D, D), dropout_p, seed, seed_dev, _stream(qkv), b64, bst)
+            ctx.dmask = _fa64_fwd(_DT[qkv.dtype], base, base + D * es, base + 2 * D * es, o, lse, B, S, S, H, H, sc,
+                                  causal, (3 * H * D, 3 * D), (3 * H * D, 3 * D), (H * D, D), dropout_p, seed, seed_dev,
+                                  _stream(qkv), b64, bst)
             ctx.b64, ctx.bst = b64, bst
             ctx.save_for_backward(qkv, o, lse)
             ctx.seed, ctx.seed_dev, ctx.causal, ctx.scale, ctx.dropout_p = seed, seed_dev, causal, sc, float(dropout_p)
@@ -1014,15 +906,13 @@ class FlashAttentionExtPacked(torch.autograd.Function):
             L = _L()
             delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
             g = torch.empty_like(qkv)
-            _check(L.pha_flash_attn_bwd_preprocess(c_int(_DT[qkv.dtype]), _ptr(o), _ptr(do), _ptr(delta), c_int(B),
-                                                   c_int(S), c_int(H), c_int(D), _stream(qkv)),
-                   "flash_attn_bwd_preprocess")
+            _check(L.pha_flash_attn_bwd_preprocess(_DT[qkv.dtype], _ptr(o), _ptr(do), _ptr(delta), B, S, H, D,
+                                                   _stream(qkv)), "flash_attn_bwd_preprocess")
             es, base, gb = qkv.element_size(), qkv.data_ptr(), g.data_ptr()
             st = (3 * H * D, 3 * D)
-            _fa64_bwd(_DT[qkv.dtype], c_void_p(base), c_void_p(base + D * es), c_void_p(base + 2 * D * es), do, lse,
-                      delta, c_void_p(gb), c_void_p(gb + D * es), c_void_p(gb + 2 * D * es), B, S, S, H, H, ctx.scale,
-                      ctx.causal, st, st, st, st, ctx.dropout_p, ctx.seed, ctx.seed_dev, _stream(qkv), ctx.dmask,
-                      ctx.b64, ctx.bst)
+            _fa64_bwd(_DT[qkv.dtype], base, base + D * es, base + 2 * D * es, do, lse, delta, gb, gb + D * es,
+                      gb + 2 * D * es, B, S, S, H, H, ctx.scale, ctx.causal, st, st, st, st, ctx.dropout_p, ctx.seed,
+                      ctx.seed_dev, _stream(qkv), ctx.dmask, ctx.b64, ctx.bst)
             return g, None, None, None, None
         q, k, v, o, lse = ctx.saved_tensors
         do = do.contiguous()
@@ -1030,15 +920,15 @@ class FlashAttentionExtPacked(torch.autograd.Function):
         L = _L()
         delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         g = torch.empty((B, S, H, 3 * D), dtype=q.dtype, device=q.device)
-        _check(L.pha_flash_attn_bwd_preprocess(c_int(_DT[q.dtype]), _ptr(o), _ptr(do), _ptr(delta), c_int(B), c_int(S),
-                                               c_int(H), c_int(D), _stream(q)), "flash_attn_bwd_preprocess")
+        _check(L.pha_flash_attn_bwd_preprocess(_DT[q.dtype], _ptr(o), _ptr(do), _ptr(delta), B, S, H, D, _stream(q)),
+               "flash_attn_bwd_preprocess")
         sb, sh, sq = ctx.strides
         es = g.element_size()
         base = g.data_ptr()
         _check(L.pha_flash_attn_bwd_ext(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), _ptr(do), _ptr(lse), _ptr(delta),
-                                        c_void_p(base), c_void_p(base + D * es), c_void_p(base + 2 * D * es), B, S, S,
-                                        H, H, D, ctx.scale, int(ctx.causal), _ptr(ctx.bias), sb, sh, sq, ctx.dropout_p,
-                                        ctx.seed, _stream(q), 3 * H * D, 3 * D, 3 * H * D, 3 * D, _ptr(ctx.seed_dev)),
+                                        base, base + D * es, base + 2 * D * es, B, S, S, H, H, D, ctx.scale,
+                                        int(ctx.causal), _ptr(ctx.bias), sb, sh, sq, ctx.dropout_p, ctx.seed,
+                                        _stream(q), 3 * H * D, 3 * D, 3 * H * D, 3 * D, _ptr(ctx.seed_dev)),
                "flash_attn_bwd_ext(packed)")
         return g, None, None, None, None
 
@@ -1078,9 +968,7 @@ def _bwd_fused(D):
     is the two-kernel v2 backward, measured faster at the GPT shape (0.95 vs 1.14 ms, B8 S2048
     H16 D128 causal: the fused kernel's one wave per SIMD exposes its LDS latency)."""
     import os
-    if D != 128 or os.environ.get("PHA_FA_BWD", "v2") != "fused" or os.environ.get("PHA_FA_BWD_V1") == "1":
-        return False
-    return hasattr(_lib.lib, "pha_flash_attn_bwd_fused")
+    return D == 128 and os.environ.get("PHA_FA_BWD", "v2") == "fused" and os.environ.get("PHA_FA_BWD_V1") != "1"
 
 
 class FlashAttention(torch.autograd.Function):
@@ -1099,10 +987,8 @@ class FlashAttention(torch.autograd.Function):
             _fa64_fwd(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), o, lse, B, S, Sk, H, Hk, sc, causal, (H * D, D),
                       (Hk * D, D), (H * D, D), 0.0, 0, None, _stream(q))
         else:
-            L = _L()
-            _check(L.pha_flash_attn_fwd(c_int(_DT[q.dtype]), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), c_int(B),
-                                        c_int(S), c_int(Sk), c_int(H), c_int(Hk), c_int(D), c_float(sc),
-                                        c_int(int(causal)), _stream(q)), "flash_attn_fwd")
+            _check(_L().pha_flash_attn_fwd(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), B, S, Sk, H, Hk,
+                                           D, sc, int(causal), _stream(q)), "flash_attn_fwd")
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.causal = causal
         ctx.scale = sc
@@ -1119,7 +1005,7 @@ class FlashAttention(torch.autograd.Function):
         dq = torch.empty_like(q)
         dk = torch.empty_like(k) if Hk == H else torch.empty((B, Sk, H, D), dtype=k.dtype, device=k.device)
         dv = torch.empty_like(v) if Hk == H else torch.empty((B, Sk, H, D), dtype=v.dtype, device=v.device)
-        _check(L.pha_flash_attn_bwd_preprocess(c_int(_DT[q.dtype]), _ptr(o), _ptr(do), _ptr(delta), c_int(B), c_int(S), c_int(H), c_int(D),
+        _check(L.pha_flash_attn_bwd_preprocess(_DT[q.dtype], _ptr(o), _ptr(do), _ptr(delta), B, S, H, D,
                                                _stream(q)), "flash_attn_bwd_preprocess")
         if getattr(ctx, "fa64", False):
             _fa64_bwd(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), do, lse, delta, _ptr(dq), _ptr(dk), _ptr(dv), B, S, Sk,
@@ -1127,15 +1013,13 @@ class FlashAttention(torch.autograd.Function):
         elif _bwd_fused(D):
             # single-kernel backward; dQ is summed over key blocks in an fp32 workspace
             acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
-            L.pha_flash_attn_bwd_fused.restype = c_int
-            _check(L.pha_flash_attn_bwd_fused(c_int(_DT[q.dtype]), _ptr(q), _ptr(k), _ptr(v), _ptr(do), _ptr(lse),
-                                              _ptr(delta), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(acc), c_int(B), c_int(S),
-                                              c_int(Sk), c_int(H), c_int(Hk), c_int(D), c_float(ctx.scale),
-                                              c_int(int(ctx.causal)), _stream(q)), "flash_attn_bwd_fused")
+            _check(L.pha_flash_attn_bwd_fused(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), _ptr(do), _ptr(lse),
+                                              _ptr(delta), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(acc), B, S, Sk, H, Hk, D,
+                                              ctx.scale, int(ctx.causal), _stream(q)), "flash_attn_bwd_fused")
         else:
-            _check(L.pha_flash_attn_bwd(c_int(_DT[q.dtype]), _ptr(q), _ptr(k), _ptr(v), _ptr(do), _ptr(lse), _ptr(delta), _ptr(dq),
-                                        _ptr(dk), _ptr(dv), c_int(B), c_int(S), c_int(Sk), c_int(H), c_int(Hk), c_int(D),
-                                        c_float(ctx.scale), c_int(int(ctx.causal)), _stream(q)), "flash_attn_bwd")
+            _check(L.pha_flash_attn_bwd(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), _ptr(do), _ptr(lse), _ptr(delta),
+                                        _ptr(dq), _ptr(dk), _ptr(dv), B, S, Sk, H, Hk, D, ctx.scale, int(ctx.causal),
+                                        _stream(q)), "flash_attn_bwd")
         if Hk != H:
             g = H // Hk
             dk = dk.view(B, Sk, Hk, g, D).sum(3)
@@ -1149,8 +1033,7 @@ def flash_attn_packed_supported(qkv, num_heads):
     if os.environ.get("PHA_DISABLE_FLASH") == "1" or os.environ.get("PHA_FA_FWD_V1") == "1" \
             or os.environ.get("PHA_FA_BWD_V1") == "1":
         return False
-    L = _lib.lib
-    return (L is not None and hasattr(L, "pha_flash_attn_fwd_packed") and qkv.is_cuda and qkv.dim() == 4
+    return (_lib.lib is not None and qkv.is_cuda and qkv.dim() == 4
             and qkv.dtype in (torch.bfloat16, torch.float16) and qkv.is_contiguous() and qkv.shape[2] == num_heads
             and qkv.shape[3] == 3 * 128)
 
@@ -1167,11 +1050,8 @@ class FlashAttentionPacked(torch.autograd.Function):
         sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(D))
         o = torch.empty((B, S, H, D), dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-        L = _L()
-        L.pha_flash_attn_fwd_packed.restype = c_int
-        _check(L.pha_flash_attn_fwd_packed(c_int(_DT[qkv.dtype]), _ptr(qkv), _ptr(o), _ptr(lse), c_int(B), c_int(S),
-                                           c_int(H), c_int(D), c_float(sc), c_int(int(causal)), _stream(qkv)),
-               "flash_attn_fwd_packed")
+        _check(_L().pha_flash_attn_fwd_packed(_DT[qkv.dtype], _ptr(qkv), _ptr(o), _ptr(lse), B, S, H, D, sc,
+                                              int(causal), _stream(qkv)), "flash_attn_fwd_packed")
         ctx.save_for_backward(qkv, o, lse)
         ctx.causal, ctx.scale = causal, sc
         return o
@@ -1183,30 +1063,20 @@ class FlashAttentionPacked(torch.autograd.Function):
         B, S, H, D3 = qkv.shape
         D = D3 // 3
         L = _L()
-        L.pha_flash_attn_bwd_packed.restype = c_int
         delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
         dqkv = torch.empty_like(qkv)
-        if not _bwd_fused(D) and hasattr(L, "pha_flash_attn_bwd_packed_od"):
+        if not _bwd_fused(D):
             # delta = rowsum(dO * O) formed inside the dQ kernel (no separate preprocess pass)
-            L.pha_flash_attn_bwd_packed_od.restype = c_int
-            _check(L.pha_flash_attn_bwd_packed_od(c_int(_DT[qkv.dtype]), _ptr(qkv), _ptr(o), _ptr(do), _ptr(lse),
-                                                  _ptr(delta), _ptr(dqkv), c_int(B), c_int(S), c_int(H), c_int(D),
-                                                  c_float(ctx.scale), c_int(int(ctx.causal)), _stream(qkv)),
-                   "flash_attn_bwd_packed_od")
+            _check(L.pha_flash_attn_bwd_packed_od(_DT[qkv.dtype], _ptr(qkv), _ptr(o), _ptr(do), _ptr(lse),
+                                                  _ptr(delta), _ptr(dqkv), B, S, H, D, ctx.scale, int(ctx.causal),
+                                                  _stream(qkv)), "flash_attn_bwd_packed_od")
             return dqkv, None, None
-        _check(L.pha_flash_attn_bwd_preprocess(c_int(_DT[qkv.dtype]), _ptr(o), _ptr(do), _ptr(delta), c_int(B),
-                                               c_int(S), c_int(H), c_int(D), _stream(qkv)), "flash_attn_bwd_preprocess")
-        if _bwd_fused(D):
-            acc = torch.empty((B, S, H, D), dtype=torch.float32, device=qkv.device)
-            L.pha_flash_attn_bwd_packed_fused.restype = c_int
-            _check(L.pha_flash_attn_bwd_packed_fused(c_int(_DT[qkv.dtype]), _ptr(qkv), _ptr(do), _ptr(lse),
-                                                     _ptr(delta), _ptr(dqkv), _ptr(acc), c_int(B), c_int(S), c_int(H),
-                                                     c_int(D), c_float(ctx.scale), c_int(int(ctx.causal)),
-                                                     _stream(qkv)), "flash_attn_bwd_packed_fused")
-        else:
-            _check(L.pha_flash_attn_bwd_packed(c_int(_DT[qkv.dtype]), _ptr(qkv), _ptr(do), _ptr(lse), _ptr(delta),
-                                               _ptr(dqkv), c_int(B), c_int(S), c_int(H), c_int(D), c_float(ctx.scale),
-                                               c_int(int(ctx.causal)), _stream(qkv)), "flash_attn_bwd_packed")
+        _check(L.pha_flash_attn_bwd_preprocess(_DT[qkv.dtype], _ptr(o), _ptr(do), _ptr(delta), B, S, H, D,
+                                               _stream(qkv)), "flash_attn_bwd_preprocess")
+        acc = torch.empty((B, S, H, D), dtype=torch.float32, device=qkv.device)
+        _check(L.pha_flash_attn_bwd_packed_fused(_DT[qkv.dtype], _ptr(qkv), _ptr(do), _ptr(lse), _ptr(delta),
+                                                 _ptr(dqkv), _ptr(acc), B, S, H, D, ctx.scale, int(ctx.causal),
+                                                 _stream(qkv)), "flash_attn_bwd_packed_fused")
         return dqkv, None, None
 
 
@@ -1214,12 +1084,7 @@ class FlashAttentionPacked(torch.autograd.Function):
 # split-KV decode attention (csrc/kernels/decode_attn.hip)
 # ----------------------------------------------------------------------------
 def _decode_attn_chunk():
-    L = _lib.lib
-    if L is None or not hasattr(L, "pha_decode_attn_chunk"):
-        return 0
-    L.pha_decode_attn_chunk.argtypes = []
-    L.pha_decode_attn_chunk.restype = c_int
-    return int(L.pha_decode_attn_chunk())
+    return 0 if _lib.lib is None else _lib.lib.pha_decode_attn_chunk()
 
 
 DECODE_ATTN_CHUNK = _decode_attn_chunk()   # key positions per split (0: library not built)
@@ -1230,7 +1095,7 @@ def decode_attn_supported(qkv, cache, mask=None, device_time_step=False):
     a [2, B, H, max_seq, D] cache of the same dtype and device, and an optional additive / boolean
     mask broadcastable to [B, H, 1, keys] that needs no gradient (with a device time step its key
     dimension must span the whole cache, or be 1)"""
-    if not DECODE_ATTN_CHUNK or _lib.lib is None or not hasattr(_lib.lib, "pha_decode_attn"):
+    if not DECODE_ATTN_CHUNK:
         return False
     if not (isinstance(qkv, torch.Tensor) and isinstance(cache, torch.Tensor) and qkv.is_cuda and cache.is_cuda):
         return False
@@ -1314,14 +1179,8 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
     ws = torch.empty((B, H, nsplit, D + 2), dtype=torch.float32, device=dev)
     out = torch.empty((B, 1, H * D), dtype=qkv.dtype, device=dev)
     sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(D))
-    L = _L()
-    if not getattr(L, "_decode_attn_sig", False):
-        P, I, LG, F = c_void_p, c_int, c_long, c_float
-        L.pha_decode_attn.argtypes = [I, P, P, P, P, LG, LG, F, I, P, P, P, I, I, I, I, P]
-        L.pha_decode_attn.restype = c_int
-        L._decode_attn_sig = True
-    _check(L.pha_decode_attn(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc, ts,
-                             _ptr(ts_dev), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
+    _check(_L().pha_decode_attn(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc, ts,
+                                _ptr(ts_dev), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
     return out
 
 
@@ -1329,44 +1188,20 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
 # weight-streaming GEMM for M <= 16 rows (csrc/kernels/skinny_gemm.hip)
 # ----------------------------------------------------------------------------
 _SKINNY_ACT = {"none": 0, "gelu": 1, "relu": 2}
-
-
-def _skinny_lib():
-    """the kernel library with the skinny-GEMM signatures set, or None where it is not built"""
-    L = _lib.lib
-    if L is None or not hasattr(L, "pha_skinny_gemm"):
-        return None
-    if not getattr(L, "_skinny_gemm_sig", False):
-        P, I, LG = c_void_p, c_int, c_long
-        IP = ctypes.POINTER(c_int)
-        L.pha_skinny_gemm_tile.argtypes = [I, IP, IP]
-        L.pha_skinny_gemm_plan.argtypes = [I, I, I, IP, IP]
-        L.pha_skinny_gemm.argtypes = [I, I, P, LG, P, P, P, P, P, I, I, I, I, I, I, P]
-        for f in (L.pha_skinny_gemm_tile, L.pha_skinny_gemm_plan, L.pha_skinny_gemm):
-            f.restype = c_int
-        L._skinny_gemm_sig = True
-    return L
-
-
 SKINNY_GEMM_MAX_M = 16   # one MFMA 16x16x32 row block
 
 
 def skinny_gemm_tile(w_is_nk):
     """(column tile, K step per iteration) of the kernel for a weight layout"""
-    L = _skinny_lib()
-    if L is None:
-        raise RuntimeError("libpha_kernels.so not loaded")
     bn, ks = c_int(0), c_int(0)
-    _check(L.pha_skinny_gemm_tile(1 if w_is_nk else 0, ctypes.byref(bn), ctypes.byref(ks)), "skinny_gemm_tile")
+    _check(_L().pha_skinny_gemm_tile(1 if w_is_nk else 0, ctypes.byref(bn), ctypes.byref(ks)), "skinny_gemm_tile")
     return bn.value, ks.value
 
 
 def skinny_gemm_plan(N, K, w_is_nk):
     """(nsplit, k_per_split) the kernel uses for an [M, K] x [K, N] product: a function of N, K and the
     weight layout alone (never M or data), so a captured graph stays valid and results reproduce"""
-    L = _skinny_lib()
-    if L is None:
-        raise RuntimeError("libpha_kernels.so not loaded")
+    L = _L()
     ns, kps = c_int(0), c_int(0)
     if int(N) < 1 or int(K) < 1:
         raise ValueError(f"skinny_gemm_plan: N={N} K={K} must be positive")
@@ -1418,7 +1253,7 @@ def skinny_gemm_supported(x, w, w_is_nk, bias=None, residual=None):
     unit inner stride and a row stride that is a multiple of 8, a contiguous w ([N, K] if ``w_is_nk``
     else [K, N]), K and N multiples of 8, contiguous bias [N] and residual [M, N], every pointer
     16-byte aligned; and an (N, K, layout) class that skinny_gemm_excluded does not name"""
-    if _skinny_lib() is None or _skinny_reject(x, w, w_is_nk, bias, residual) is not None:
+    if _lib.lib is None or _skinny_reject(x, w, w_is_nk, bias, residual) is not None:
         return False
     N = w.shape[0] if w_is_nk else w.shape[1]
     return not skinny_gemm_excluded(N, x.shape[1], w_is_nk)
@@ -1433,8 +1268,8 @@ def skinny_gemm_excluded(N, K, w_is_nk):
 
 def skinny_gemm_why_not(x, w, w_is_nk, bias=None, residual=None):
     """the reason skinny_gemm would reject these arguments, for the fallback log"""
-    if _skinny_lib() is None:
-        return "kernel library without pha_skinny_gemm"
+    if _lib.lib is None:
+        return "kernel library not loaded"
     return _skinny_reject(x, w, w_is_nk, bias, residual) or "supported"
 
 
@@ -1450,9 +1285,7 @@ def skinny_gemm(x, w, w_is_nk, bias=None, act="none", residual=None, nsplit=None
         raise ValueError(f"{fn}: {why}")
     if act not in _SKINNY_ACT:
         raise ValueError(f"{fn}: act must be one of {sorted(_SKINNY_ACT)}, got {act!r}")
-    L = _skinny_lib()
-    if L is None:
-        raise RuntimeError("libpha_kernels.so not loaded")
+    L = _L()
     M, K = x.shape
     N = w.shape[0] if w_is_nk else w.shape[1]
     if nsplit is None:

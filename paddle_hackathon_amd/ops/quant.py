@@ -12,29 +12,12 @@ pass, moving-average scale update). Scales are fp32 device tensors; nothing here
 with the host."""
 from __future__ import annotations
 
-from ctypes import c_float, c_int, c_long, c_void_p
-
 import torch
 
 from . import _lib
+from ._abi import DT as _DT, check as _chk, ptr as _ptr, stream as _st
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
-
-def _L():
-    L = _lib._load()
-    if L is None:
-        raise RuntimeError(f"libpha_kernels.so not loaded: {_lib._load_error}")
-    if not getattr(L, "_quant_sig", False):
-        P, I, LG = c_void_p, c_int, c_long
-        L.pha_quant_absmax.argtypes = [I, P, LG, P, P]
-        L.pha_quant_channel_absmax.argtypes = [I, P, LG, LG, LG, P, P]
-        L.pha_quant_dequant.argtypes = [I, I, P, P, LG, LG, LG, P, I, I, I, P]
-        L.pha_quant_moving_avg.argtypes = [P, P, P, P, c_float, P]
-        for f in (L.pha_quant_absmax, L.pha_quant_channel_absmax, L.pha_quant_dequant, L.pha_quant_moving_avg):
-            f.restype = c_int
-        L._quant_sig = True
-    return L
+_L = _lib.loaded
 
 
 def _native(x):
@@ -48,15 +31,6 @@ def _native(x):
 def _prep(x):
     x = x.contiguous()
     return x if x.data_ptr() % 16 == 0 else x.clone()
-
-
-def _st(x):
-    return c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-
-
-def _chk(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc})")
 
 
 def bin_cnt(bits):
@@ -81,8 +55,7 @@ def abs_max(x):
     if _native(x):
         x = _prep(x)
         out = torch.empty(1, dtype=torch.float32, device=x.device)
-        _chk(_L().pha_quant_absmax(_DT[x.dtype], c_void_p(x.data_ptr()), x.numel(), c_void_p(out.data_ptr()), _st(x)),
-             "pha_quant_absmax")
+        _chk(_L().pha_quant_absmax(_DT[x.dtype], _ptr(x), x.numel(), _ptr(out), _st(x)), "pha_quant_absmax")
         return out
     return x.abs().max().float().reshape(1) if x.numel() else torch.zeros(1, device=x.device)
 
@@ -94,8 +67,8 @@ def channel_abs_max(x, quant_axis=0):
     if _native(x):
         x = _prep(x)
         out = torch.empty(C, dtype=torch.float32, device=x.device)
-        _chk(_L().pha_quant_channel_absmax(_DT[x.dtype], c_void_p(x.data_ptr()), outer, C, inner,
-                                           c_void_p(out.data_ptr()), _st(x)), "pha_quant_channel_absmax")
+        _chk(_L().pha_quant_channel_absmax(_DT[x.dtype], _ptr(x), outer, C, inner, _ptr(out), _st(x)),
+             "pha_quant_channel_absmax")
         return out
     return x.abs().float().reshape(outer, C, inner).amax(dim=(0, 2))
 
@@ -103,8 +76,8 @@ def channel_abs_max(x, quant_axis=0):
 def moving_average_update(cur, state, accum, scale, rate):
     """in place: state = r*state + 1, accum = r*accum + cur, scale = accum / state (fp32 [1] each)"""
     if cur.is_cuda and _lib.require_native():
-        _chk(_L().pha_quant_moving_avg(*(c_void_p(t.data_ptr()) for t in (cur, state, accum, scale)), float(rate),
-                                       _st(cur)), "pha_quant_moving_avg")
+        _chk(_L().pha_quant_moving_avg(_ptr(cur), _ptr(state), _ptr(accum), _ptr(scale), float(rate), _st(cur)),
+             "pha_quant_moving_avg")
         return
     with torch.no_grad():
         state.mul_(rate).add_(1.0)
@@ -146,9 +119,8 @@ def quant_dequant(x, scale, bits=8, round_type=1, dequant=True, quant_axis=None,
         x = _prep(x)
         scale = scale.detach().float().contiguous()
         y = torch.empty(x.shape, dtype=od, device=x.device)
-        _chk(_L().pha_quant_dequant(_DT[x.dtype], _DT[od], c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), x.numel(),
-                                    C, inner, c_void_p(scale.data_ptr()), int(bits), int(round_type), int(dequant),
-                                    _st(x)), "pha_quant_dequant")
+        _chk(_L().pha_quant_dequant(_DT[x.dtype], _DT[od], _ptr(x), _ptr(y), x.numel(), C, inner, _ptr(scale),
+                                    int(bits), int(round_type), int(dequant), _st(x)), "pha_quant_dequant")
         return y
     return _qdq_torch(x, scale, bits, round_type, dequant, C, inner).to(od)
 

@@ -12,37 +12,13 @@ Weight list order is the reference's ``RNNBase._all_weights`` (rnn.py:953-962): 
 (layer, direction)'s ``weight_ih, weight_hh`` first, then every ``bias_ih, bias_hh``."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
+
+from ._abi import ptr as _p, stream as _stream
+from ._lib import loaded as _lib   # a GPU run without the kernel library fails loudly
 
 MODES = {"RNN_TANH": 0, "RNN_RELU": 1, "LSTM": 2, "GRU": 3}
 GATES = {0: 1, 1: 1, 2: 4, 3: 3}
-
-
-def _lib():
-    from . import _lib as m
-    L = m._load()
-    if L is None:   # a GPU run without the kernel library fails loudly
-        m.require_native()
-        raise RuntimeError("paddle_hackathon_amd: HIP kernel library unavailable for the rnn op")
-    if not getattr(L, "_pha_rnn_sig", False):
-        p = ctypes.c_void_p
-        i = ctypes.c_int
-        L.pha_rnn_fwd.argtypes = [i, i, i, i, p, p, p, p, p, p, p, p, i, p]
-        L.pha_rnn_fwd.restype = i
-        L.pha_rnn_bwd.argtypes = [i, i, i, i, p, p, p, p, p, p, p, p, p, p, p, i, p]
-        L.pha_rnn_bwd.restype = i
-        L._pha_rnn_sig = True
-    return L
-
-
-def _p(t):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 class _Recur(torch.autograd.Function):

@@ -85,23 +85,13 @@ class GpuPsTable:
             return torch.zeros(0, dtype=torch.int32, device=self.device)
         if self.gpu:
             from ...ops.hip import _L, _ptr, _stream
-            from ctypes import c_float, c_int, c_long, c_uint, c_void_p
-            L = _L()
-            if not getattr(L, "_gps_sig", False):
-                L.pha_ps_gpu_find.argtypes = [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_int,
-                                              c_int, c_void_p, c_void_p, c_int, c_uint, c_float, c_void_p]
-                L.pha_ps_gpu_find.restype = c_int
-                L.pha_ps_gpu_adagrad.argtypes = [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_float,
-                                                 c_float, c_float, c_float, c_void_p]
-                L.pha_ps_gpu_adagrad.restype = c_int
-                L._gps_sig = True
             keys = keys.contiguous()
             if bool(((keys == _EMPTY) | (keys == _TOMB)).any()):
                 raise ValueError("GPU-PS keys -1 and -2 are reserved (empty / tombstone slot markers)")
             rows = torch.empty(n, dtype=torch.int32, device=self.device)
-            rc = L.pha_ps_gpu_find(_ptr(keys), _ptr(rows), n, _ptr(self.keys), _ptr(self.rows), self.capacity,
-                                   _ptr(self.next_row), self.max_rows, int(create), _ptr(self.W), _ptr(self.g2),
-                                   self.dim, self.seed, self.init_range, _stream(self.W))
+            rc = _L().pha_ps_gpu_find(_ptr(keys), _ptr(rows), n, _ptr(self.keys), _ptr(self.rows), self.capacity,
+                                      _ptr(self.next_row), self.max_rows, int(create), _ptr(self.W), _ptr(self.g2),
+                                      self.dim, self.seed, self.init_range, _stream(self.W))
             if rc != 0:
                 raise RuntimeError(f"pha_ps_gpu_find failed ({rc})")
             if create and bool((rows < -1).any()):

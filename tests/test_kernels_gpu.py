@@ -462,6 +462,59 @@ def test_flash_attention_qkv_packed(causal, S):
     assert err < 3e-2 * max(1.0, qr.grad.abs().max().item()), err
 
 
+def _packed_case(causal):
+    """one 128-query block of packed [B, S, H, 3D] attention: (qkv, dO, fp32 output, fp32 dqkv)"""
+    torch.manual_seed(5)
+    B, S, H, D = 1, 128, 2, 128
+    qkv = torch.randn(B, S, H, 3 * D, device="cuda").bfloat16()
+    do = torch.randn(B, S, H, D, device="cuda").bfloat16()
+    qr = qkv.float().requires_grad_(True)
+    ref = _ref_attn(*qr.split(D, dim=-1), causal)
+    (gref,) = torch.autograd.grad(ref, qr, do.float())
+    return qkv, do, ref.detach(), gref
+
+
+@pytest.mark.parametrize("causal", [False, True])
+def test_flash_attention_qkv_packed_fused_bwd(causal, monkeypatch):
+    """PHA_FA_BWD=fused on the packed path: preprocess + the single-kernel backward writing dq | dk |
+    dv into one packed gradient (pha_flash_attn_bwd_packed_fused) == fp32 SDPA"""
+    from paddle_hackathon_amd.ops import hip
+    monkeypatch.setenv("PHA_FA_BWD", "fused")
+    L, calls = hip._L(), []
+    real = L.pha_flash_attn_bwd_packed_fused
+    monkeypatch.setattr(L, "pha_flash_attn_bwd_packed_fused", lambda *a: calls.append(1) or real(*a))
+    qkv, do, ref, gref = _packed_case(causal)
+    a = qkv.clone().requires_grad_(True)
+    o = hip.FlashAttentionPacked.apply(a, causal, None)
+    assert (o.float() - ref).abs().max().item() < 2e-2
+    (g,) = torch.autograd.grad(o, a, do)
+    assert calls, "the packed backward did not take the fused kernel"
+    err = (g.float() - gref).abs().max().item()
+    assert err < 3e-2 * max(1.0, gref.abs().max().item()), err
+
+
+@pytest.mark.parametrize("causal", [False, True])
+def test_flash_attention_bwd_packed_entry_point(causal):
+    """pha_flash_attn_bwd_packed (the packed two-kernel backward reading a delta computed by the
+    separate preprocess pass; the bindings call its _od sibling) called as exported == fp32 SDPA"""
+    from paddle_hackathon_amd.ops import hip
+    from paddle_hackathon_amd.ops.hip import _DT, _ptr, _stream
+    qkv, do, ref, gref = _packed_case(causal)
+    B, S, H, D = do.shape
+    L, dt, sc, st = hip._L(), _DT[qkv.dtype], 1.0 / math.sqrt(D), _stream(qkv)
+    o = torch.empty_like(do)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device="cuda")
+    delta = torch.empty(B, H, S, dtype=torch.float32, device="cuda")
+    g = torch.empty_like(qkv)
+    assert L.pha_flash_attn_fwd_packed(dt, _ptr(qkv), _ptr(o), _ptr(lse), B, S, H, D, sc, int(causal), st) == 0
+    assert (o.float() - ref).abs().max().item() < 2e-2
+    assert L.pha_flash_attn_bwd_preprocess(dt, _ptr(o), _ptr(do), _ptr(delta), B, S, H, D, st) == 0
+    assert L.pha_flash_attn_bwd_packed(dt, _ptr(qkv), _ptr(do), _ptr(lse), _ptr(delta), _ptr(g), B, S, H, D, sc,
+                                       int(causal), st) == 0
+    err = (g.float() - gref).abs().max().item()
+    assert err < 3e-2 * max(1.0, gref.abs().max().item()), err
+
+
 # ----------------------------------------------------------------------------- batch norm (NHWC)
 def _bn_ref(x, w, b, res, relu, eps):
     xf = x.float()
