@@ -19,8 +19,8 @@
 //
 // Split-K is deterministic: the plan depends on (N, K, layout) alone, split s writes its fp32
 // partial to ws[s, M, N] with plain stores, and skinny_finish sums the splits in a fixed order and
-// applies the epilogue (bias, erf-GELU / ReLU, residual, one rounding). With one split the first
-// kernel applies the epilogue itself. No atomics; two plain launches on the caller's stream.
+// applies the epilogue (bias, erf-GELU / tanh-GELU / ReLU, residual, one rounding). With one split the
+// first kernel applies the epilogue itself. No atomics; two plain launches on the caller's stream.
 //
 // Tails: N % 8 == K % 8 == 0, so a 16-byte piece is wholly inside or outside. Column pieces
 // outside N load a clamped (valid) address and their results are never stored; k pieces outside
@@ -40,7 +40,7 @@ constexpr int TARGET_WAVES = 1024;            // 4 streaming waves on each of 25
 constexpr int MAX_SPLIT = 32;
 constexpr int FIN_Q = 32, FIN_J = 8, FIN_THREADS = FIN_Q * FIN_J;
 
-enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
+enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_GELU_TANH = 3 };
 enum Layout : int { LAYOUT_KN = 0, LAYOUT_NK = 1 };
 
 // fragments stay in a native vector type (selects and array elements of it live in registers)
@@ -54,6 +54,11 @@ __device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, const f32x4
 __device__ __forceinline__ float act_apply(float v, int act) {
   if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.7071067811865476f));
   if (act == ACT_RELU) return fmaxf(v, 0.f);
+  if (act == ACT_GELU_TANH) {   // gelu_f(x, approx) of ce_gelu_embed.hip: what the GPT MLP trains with
+    const float u = 0.7978845608028654f * (v + 0.044715f * v * v * v);
+    const float th = 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * u) + 1.f);
+    return 0.5f * v * (1.f + th);
+  }
   return v;
 }
 
@@ -308,7 +313,7 @@ PHA_API int pha_skinny_gemm(int dt, int layout, const void* x, long ldx, const v
                             const void* residual, void* out, float* ws, int M, int N, int K, int nsplit,
                             int k_per_split, int act, hipStream_t stream) {
   if (M < 1 || M > pha::sk::MAX_M || N < 8 || K < 8 || N % 8 || K % 8 || ldx < K || ldx % 8) return (int)hipErrorInvalidValue;
-  if ((layout != 0 && layout != 1) || act < 0 || act > 2 || !x || !w || !out) return (int)hipErrorInvalidValue;
+  if ((layout != 0 && layout != 1) || act < 0 || act > 3 || !x || !w || !out) return (int)hipErrorInvalidValue;
   if (nsplit < 1 || nsplit > 65535 || k_per_split < 8 || k_per_split % 8) return (int)hipErrorInvalidValue;
   if ((long)(nsplit - 1) * k_per_split >= K || (long)nsplit * k_per_split < K) return (int)hipErrorInvalidValue;
   if (nsplit > 1 && !ws) return (int)hipErrorInvalidValue;

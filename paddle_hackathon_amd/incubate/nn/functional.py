@@ -50,6 +50,8 @@ def _ln(x, w, b, eps):
 def _act(x, bias, activation):
     if activation == "gelu":
         return _ops.fused.bias_gelu(x, bias, False) if bias is not None else _ops.fused.gelu(x, False)
+    if activation == "gelu_tanh":
+        return _ops.fused.bias_gelu(x, bias, True) if bias is not None else _ops.fused.gelu(x, True)
     h = x + bias if bias is not None else x
     if activation == "relu":
         return torch.relu(h)
@@ -74,7 +76,7 @@ def _skinny_ok(x2, w, w_is_nk, bias=None, residual=None):
     if _ops.hip.skinny_gemm_supported(x2, w, w_is_nk, bias, residual):
         return True
     N, K = (w.shape[0], w.shape[1]) if w_is_nk else (w.shape[1], w.shape[0])
-    if _ops.hip.skinny_gemm_excluded(N, K, w_is_nk):
+    if _ops.hip.skinny_gemm_excluded(N, K, w_is_nk, x2.shape[0]):
         return False
     from ...ops import fallback
     fallback.note("decode_gemm", f"{_ops.hip.skinny_gemm_why_not(x2, w, w_is_nk, bias, residual)} -> library GEMM")
@@ -255,6 +257,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     products of each layer run on the weight-streaming kernels (csrc/kernels/skinny_gemm.hip): QKV in
     either ``trans_qkvw`` layout without a transposed copy, the output projection and ffn2 with bias
     and residual add in the epilogue (where dropout is an identity and ``ring_id < 0``), ffn1 with bias + GELU / ReLU.
+    ``activation`` is "gelu" (erf), "gelu_tanh" (the tanh approximation the GPT model trains with) or "relu".
     PHA_DECODE_GEMM=0 keeps the library GEMMs and the separate elementwise passes."""
     h = _u(x)
     B, S, E = h.shape
@@ -344,7 +347,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         residual = h
         f = _ln(h, _u(ffn_ln_scales[i]), _u(ffn_ln_biases[i]), epsilon) if pre_layer_norm else h
         w1, b1 = _u(ffn1_weights[i]), _u(ffn1_biases[i]) if ffn1_biases is not None else None
-        f1 = _skinny_linear(f, w1, b1, activation) if skinny and activation in ("gelu", "relu") else None
+        f1 = _skinny_linear(f, w1, b1, activation) if skinny and activation in ("gelu", "gelu_tanh", "relu") else None
         f = f1 if f1 is not None else _act(f @ w1, b1, activation)
         w2f, b2 = _u(ffn2_weights[i]), _u(ffn2_biases[i]) if ffn2_biases is not None else None
         f2 = _skinny_linear(f, w2f, b2, "none", residual if epi else None) if skinny else None

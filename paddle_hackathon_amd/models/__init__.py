@@ -2,3 +2,4 @@
 from .gpt import GPTConfig, GPTForPretraining, GPTModel, gpt_config, gpt_1_3b, gpt_pretraining_loss  # noqa: F401
 from .gpt import GPTForPretrainingPipe, GPTEmbeddingPipe, GPTPretrainingCriterionPipe  # noqa: F401
 from .bert import BertConfig, BertModel, BertForPretraining, BertPretrainingCriterion, bert_config  # noqa: F401,E402
+from .gpt_generate import GPTGenerator  # noqa: F401,E402

@@ -269,6 +269,15 @@ class GPTForPretraining(nn.Layer):
             h = _c_identity(h)
         return _wrap(_cg.matmul_nt(h._t, w._t))
 
+    def generate(self, input_ids, max_new_tokens, **kwargs):
+        """cached generation (greedy search or temperature / top-k / top-p sampling) with a KV cache:
+        ``models.gpt_generate.GPTGenerator.generate`` on a generator kept with the model"""
+        gen = self.__dict__.get("_generator")
+        if gen is None:
+            from .gpt_generate import GPTGenerator
+            gen = self.__dict__["_generator"] = GPTGenerator(self)
+        return gen.generate(input_ids, max_new_tokens, **kwargs)
+
     def forward(self, input_ids, labels=None, loss_mask=None, position_ids=None):
         h = self.gpt(input_ids, position_ids)
         logits = self.logits(h)

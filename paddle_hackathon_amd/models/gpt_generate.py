@@ -1,0 +1,266 @@
+"""Cached text generation for ``GPTForPretraining``.
+
+One token costs one decode step instead of a forward over the whole prefix: the prompt runs once
+through the context stage of ``incubate.nn.functional.fused_multi_transformer``, which fills
+preallocated ``[2, B, H, prompt + max_new, D]`` key / value caches, and every further token runs
+
+    word + position embedding (the position gathered with the int32 device ``time_step``)
+    -> fused_multi_transformer(..., time_step=ts, activation="gelu_tanh")   split-KV decode attention,
+                                                                            weight-streaming GEMMs
+    -> final LayerNorm -> LM head (the tied embedding, [V, E], on skinny_gemm with at most 16 rows)
+    -> ops.hip.sample_logits -> time_step += 1
+
+with nothing in the step that syncs the host, so on the GPU the whole step is captured once in a
+hipGraph and replayed per token.
+
+The model's own parameters are used: ``nn.Linear`` weights are ``[in, out]``, the ``[K, N]`` layout
+of the kernels, and go in as views. The one exception is the fused QKV projection, whose outputs are
+ordered (head, 3, D) while the decode kernels need (3, head, D): the generator keeps one repacked
+copy of each layer's QKV weight (``[E, 3, H, D]``, passed with ``trans_qkvw=False``) and bias, and
+refreshes it in place when the parameter's version counter changes. At GPT-3 1.3B that copy is
+25 MB per layer (600 MB for the 24 layers in bf16).
+"""
+from __future__ import annotations
+
+import os
+
+import torch
+
+from ..framework.core import Tensor, _wrap
+from .. import ops as _ops
+from ..ops import conv_gemm as _cg
+
+STRATEGIES = ("greedy_search", "sampling")
+EOS_CHECK_EVERY = 16   # decode steps between two host reads of finished.all()
+
+
+class _GraphState:
+    """the static buffers of one captured decode step, and the graph once it exists"""
+
+    def __init__(self, B, cache_len, cfg, dtype, device):
+        H, D = cfg.num_heads, cfg.head_dim
+        self.caches = [torch.zeros(2, B, H, cache_len, D, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
+        self.tok = torch.zeros(B, dtype=torch.int64, device=device)
+        self.ts = torch.zeros(1, dtype=torch.int32, device=device)
+        self.u = torch.zeros(B, dtype=torch.float32, device=device)
+        self.finished = torch.zeros(B, dtype=torch.uint8, device=device)
+        self.ids = self.logprob = None
+        self.graph = None
+        self.weights_at = None
+
+
+class GPTGenerator:
+    """Cached generation over a ``GPTForPretraining`` (see the module docstring)."""
+
+    def __init__(self, model):
+        self.model = model
+        self._qkv = {}        # layer index -> (weight version, bias version, repacked weight, repacked bias)
+        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad) -> _GraphState
+        self._eager = set()   # keys whose warm-up step left the kernel path: not tried again
+        self.captures = 0     # hipGraph captures so far (a second generate call adds none)
+        self.last_caches = None
+        self.last_steps = 0   # decode steps the last call ran (fewer than max_new_tokens - 1 after an early stop)
+
+    def clear(self):
+        """drop the captured graphs with their static buffers (each key holds its own KV caches) and
+        the repacked QKV copies; the next call builds what it needs again"""
+        self._graphs.clear()
+        self._eager.clear()
+        self._qkv.clear()
+
+    # ------------------------------------------------------------------------------ weights
+    def _layer_weights(self):
+        cfg = self.model.cfg
+        H, D, E = cfg.num_heads, cfg.head_dim, cfg.hidden_size
+        names = ("ln_s", "ln_b", "qkv_w", "qkv_b", "out_w", "out_b", "fln_s", "fln_b", "f1_w", "f1_b", "f2_w", "f2_b")
+        w = {k: [] for k in names}
+        for i, layer in enumerate(self.model.gpt.layers):
+            qw, qb = layer.self_attn.qkv_proj.weight._t, layer.self_attn.qkv_proj.bias._t
+            ent = self._qkv.get(i)
+            if ent is None or ent[2].dtype != qw.dtype or ent[2].device != qw.device:
+                ent = (-1, -1, torch.empty(E, 3, H, D, dtype=qw.dtype, device=qw.device),
+                       torch.empty(3, H, D, dtype=qb.dtype, device=qb.device))
+            if ent[0] != qw._version or ent[1] != qb._version:
+                ent[2].copy_(qw.detach().view(E, H, 3, D).permute(0, 2, 1, 3))   # in place: a captured graph reads it
+                ent[3].copy_(qb.detach().view(H, 3, D).permute(1, 0, 2))
+                ent = (qw._version, qb._version, ent[2], ent[3])
+            self._qkv[i] = ent
+            w["ln_s"].append(layer.norm1.weight._t)
+            w["ln_b"].append(layer.norm1.bias._t)
+            w["qkv_w"].append(ent[2])
+            w["qkv_b"].append(ent[3])
+            w["out_w"].append(layer.self_attn.out_proj.weight._t)
+            w["out_b"].append(layer.self_attn.out_proj.bias._t)
+            w["fln_s"].append(layer.norm2.weight._t)
+            w["fln_b"].append(layer.norm2.bias._t)
+            w["f1_w"].append(layer.mlp.linear1.weight._t)
+            w["f1_b"].append(layer.mlp.linear1.bias._t)
+            w["f2_w"].append(layer.mlp.linear2.weight._t)
+            w["f2_b"].append(layer.mlp.linear2.bias._t)
+        return [w[k] for k in names]
+
+    def _stack(self, x, weights, caches, time_step=None):
+        from ..incubate.nn import functional as FF
+        out, _ = FF.fused_multi_transformer(x, *weights, pre_layer_norm=True, epsilon=self.model.cfg.layer_norm_eps,
+                                            cache_kvs=caches, time_step=time_step, activation="gelu_tanh",
+                                            trans_qkvw=False)
+        return out._t
+
+    def _logits(self, h):
+        """final LayerNorm and LM head of h [B, E] -> [B, V]"""
+        from ..incubate.nn import functional as FF
+        h = self.model.gpt.final_norm(_wrap(h))._t
+        w = self.model.gpt.embeddings.word_embeddings.weight._t
+        if h.is_cuda and h.shape[0] <= _ops.hip.SKINNY_GEMM_MAX_M and FF._skinny_ok(h, w, True):
+            return _ops.hip.skinny_gemm(h, w, True)
+        return _cg.matmul_nt(h, w)
+
+    def _sample(self, logits, u, finished, s):
+        top_k = 1 if s["strategy"] == "greedy_search" else s["top_k"]
+        args = (logits, u, s["temperature"], top_k, s["top_p"], finished, s["eos"], s["pad"])
+        if logits.shape[0] > _ops.hip.SAMPLE_MAX_B:   # more rows than a decode batch: no kernel for it
+            return _ops.hip._sample_logits_composite(*args)
+        return _ops.hip.sample_logits(*args)
+
+    def _step(self, weights, st, s, host_ts=None):
+        """one token: reads st.tok / st.ts / st.u, appends to st.caches, writes the new token to st.tok,
+        advances st.ts; returns (ids, logprob)"""
+        emb = self.model.gpt.embeddings
+        x = _ops.fused.embedding(st.tok, emb.word_embeddings.weight._t) \
+            + emb.position_embeddings.weight._t.index_select(0, st.ts)
+        h = self._stack(x.unsqueeze(1), weights, st.caches, st.ts if host_ts is None else host_ts)
+        ids, lp = self._sample(self._logits(h.reshape(h.shape[0], -1)), st.u, st.finished, s)
+        st.tok.copy_(ids)
+        st.ts.add_(1)
+        return ids, lp
+
+    # ------------------------------------------------------------------------------ generate
+    @torch.no_grad()
+    def generate(self, input_ids, max_new_tokens, decode_strategy="greedy_search", temperature=1.0, top_k=0, top_p=1.0,
+                 eos_token_id=None, pad_token_id=0, seed=None, use_graph=None):
+        """``max_new_tokens`` tokens after ``input_ids`` [B, prompt]: (ids int64 [B, max_new_tokens],
+        scores fp32 [B, max_new_tokens]), the score being the log probability of the token under the
+        temperature-scaled, unfiltered softmax (0 at padded positions).
+
+        ``decode_strategy`` "greedy_search" takes the argmax; "sampling" draws through
+        ``ops.hip.sample_logits`` with ``temperature``, ``top_k`` and ``top_p``, its uniforms from
+        ``torch.rand`` on a generator seeded with ``seed`` (None: the global generator). Within one mode
+        a seed reproduces its output; eager and graph mode are required to agree for greedy search only.
+        With ``eos_token_id`` a row that emits it is padded with ``pad_token_id`` from then on, and the
+        loop reads ``finished.all()`` every 16 steps to stop early; nothing else syncs the host.
+
+        All prompts have one length: padded prompts and ``attention_mask`` are not supported. The
+        model must be in eval mode with ``tensor_parallel_degree == 1``, and
+        ``prompt + max_new_tokens <= max_position_embeddings``.
+
+        ``use_graph`` None captures the decode step in one hipGraph when the model is on the GPU and
+        a warm-up step took the kernel path everywhere (no recorded fallback, device-side time step);
+        True insists on it, False runs the same step eagerly. The graph and its static buffers are kept
+        on the generator per (B, cache length, strategy, temperature, top_k, top_p, eos, pad), KV caches
+        included; ``GPTGenerator.clear()`` releases them."""
+        model, cfg = self.model, self.model.cfg
+        if cfg.tensor_parallel_degree != 1:
+            raise ValueError("generate: tensor_parallel_degree must be 1")
+        if model.training:
+            raise RuntimeError("generate: the model is in training mode; call model.eval() first")
+        if decode_strategy not in STRATEGIES:
+            raise ValueError(f"generate: decode_strategy must be one of {STRATEGIES}, got {decode_strategy!r}")
+        ids_in = input_ids._t if isinstance(input_ids, Tensor) else torch.as_tensor(input_ids)
+        if ids_in.dim() != 2 or ids_in.shape[0] < 1 or ids_in.shape[1] < 1:
+            raise ValueError(f"generate: input_ids must be [B, prompt], got {tuple(ids_in.shape)}")
+        B, P = ids_in.shape
+        n_new = int(max_new_tokens)
+        if n_new < 1:
+            raise ValueError(f"generate: max_new_tokens={max_new_tokens} must be at least 1")
+        if P + n_new > cfg.max_position_embeddings:
+            raise ValueError(f"generate: prompt {P} + max_new_tokens {n_new} exceeds max_position_embeddings "
+                             f"{cfg.max_position_embeddings}")
+        wte = model.gpt.embeddings.word_embeddings.weight._t
+        dev, dtype = wte.device, wte.dtype
+        ids_in = ids_in.to(device=dev, dtype=torch.int64)
+        s = dict(strategy=decode_strategy, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
+                 eos=-1 if eos_token_id is None else int(eos_token_id), pad=int(pad_token_id))
+        if use_graph and not wte.is_cuda:
+            raise RuntimeError("generate: use_graph=True needs the model on a GPU")
+        cache_len = P + n_new
+        key = (B, cache_len, s["strategy"], s["temperature"], s["top_k"], s["top_p"], s["eos"], s["pad"])
+        weights = self._layer_weights()
+        want_graph = wte.is_cuda and use_graph is not False and n_new > 1 \
+            and (bool(use_graph) or key not in self._eager)
+        st = self._graphs.get(key) if want_graph else None
+        if st is None:
+            st = _GraphState(B, cache_len, cfg, dtype, dev)
+        else:
+            for c in st.caches:
+                c.zero_()
+            st.finished.zero_()
+        self.last_caches = st.caches
+
+        # uniforms of every step, drawn up front (no per-step generator state in a captured graph)
+        gen = None
+        if seed is not None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+        U = torch.rand(n_new, B, generator=gen, device=dev, dtype=torch.float32)
+        out_ids = torch.full((B, n_new), s["pad"], dtype=torch.int64, device=dev)
+        out_lp = torch.zeros((B, n_new), dtype=torch.float32, device=dev)
+
+        # prefill: the context stage fills the caches; the first token comes from the last position
+        x = model.gpt.embeddings(_wrap(ids_in))._t
+        h = self._stack(x, weights, st.caches)
+        ids, lp = self._sample(self._logits(h[:, -1].contiguous()), U[0].contiguous(), st.finished, s)
+        out_ids[:, 0], out_lp[:, 0] = ids, lp
+        st.tok.copy_(ids)
+        st.ts.fill_(P)
+
+        graph = None
+        if want_graph:
+            graph = self._graph_for(st, weights, s, P, required=bool(use_graph))
+            if graph is not None:
+                self._graphs[key] = st
+            else:
+                self._eager.add(key)
+        host_ts = None if wte.is_cuda else P   # on the CPU the composite takes the step as a Python int
+        self.last_steps = 0
+        for j in range(1, n_new):
+            self.last_steps = j
+            st.u.copy_(U[j])
+            if graph is not None:
+                graph.replay()
+                ids, lp = st.ids, st.logprob
+            else:
+                ids, lp = self._step(weights, st, s, host_ts)
+                if host_ts is not None:
+                    host_ts += 1
+            out_ids[:, j], out_lp[:, j] = ids, lp
+            if s["eos"] >= 0 and j % EOS_CHECK_EVERY == 0 and bool(st.finished.all()):
+                break
+        return _wrap(out_ids), _wrap(out_lp)
+
+    def _graph_for(self, st, weights, s, P, required):
+        """the captured step of ``st`` (captured now if it is new or the weights moved), or None where
+        the warm-up step shows that a piece of it left the kernel path and the graph was not required"""
+        at = tuple(t.data_ptr() for group in weights for t in group)
+        if st.graph is not None and st.weights_at == at:
+            return st.graph
+        from ..ops import fallback
+        keep = (st.tok.clone(), st.finished.clone())
+        before = fallback.total()
+        self._step(weights, st, s)   # warm-up: what it appends at position P is rewritten by the first replay
+        clean = fallback.total() == before and os.environ.get("PHA_DECODE_ATTN", "1") != "0" \
+            and st.caches[0].dtype in (torch.bfloat16, torch.float16) and self.model.cfg.head_dim in (32, 64, 128)
+        st.tok.copy_(keep[0])
+        st.finished.copy_(keep[1])
+        st.ts.fill_(P)
+        if not clean and not required:
+            for c in st.caches:
+                c[:, :, :, P].zero_()
+            return None
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            st.ids, st.logprob = self._step(weights, st, s)
+        self.captures += 1
+        st.ts.fill_(P)   # capture launches nothing: the first replay is step 0
+        st.graph, st.weights_at = g, at
+        return g

@@ -121,6 +121,9 @@ SIGNATURES = {
     # rnn.hip
     "pha_rnn_fwd": (I, [I, I, I, I, P, P, P, P, P, P, P, P, I, P]),
     "pha_rnn_bwd": (I, [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I, P]),
+    # sampling.hip
+    "pha_sample_logits_max_v": (I, []),
+    "pha_sample_logits": (I, [I, P, LG, P, P, P, P, I, I, F, I, F, LG, LG, P]),
     # skinny_gemm.hip
     "pha_skinny_gemm_tile": (I, [I, P, P]),
     "pha_skinny_gemm_plan": (I, [I, I, I, P, P]),

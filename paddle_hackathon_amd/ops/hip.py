@@ -1187,7 +1187,7 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
 # ----------------------------------------------------------------------------
 # weight-streaming GEMM for M <= 16 rows (csrc/kernels/skinny_gemm.hip)
 # ----------------------------------------------------------------------------
-_SKINNY_ACT = {"none": 0, "gelu": 1, "relu": 2}
+_SKINNY_ACT = {"none": 0, "gelu": 1, "relu": 2, "gelu_tanh": 3}
 SKINNY_GEMM_MAX_M = 16   # one MFMA 16x16x32 row block
 
 
@@ -1252,18 +1252,23 @@ def skinny_gemm_supported(x, w, w_is_nk, bias=None, residual=None):
     """what skinny_gemm takes: bf16 / fp16 tensors of one dtype on one GPU, x [M, K] with 1 <= M <= 16,
     unit inner stride and a row stride that is a multiple of 8, a contiguous w ([N, K] if ``w_is_nk``
     else [K, N]), K and N multiples of 8, contiguous bias [N] and residual [M, N], every pointer
-    16-byte aligned; and an (N, K, layout) class that skinny_gemm_excluded does not name"""
+    16-byte aligned; and an (N, K, layout, M) class that skinny_gemm_excluded does not name"""
     if _lib.lib is None or _skinny_reject(x, w, w_is_nk, bias, residual) is not None:
         return False
     N = w.shape[0] if w_is_nk else w.shape[1]
-    return not skinny_gemm_excluded(N, x.shape[1], w_is_nk)
+    return not skinny_gemm_excluded(N, x.shape[1], w_is_nk, x.shape[0])
 
 
-def skinny_gemm_excluded(N, K, w_is_nk):
-    """(N, K, layout) classes that lost to the library call plus its elementwise passes in
-    tools/bench_decode_gemm.py part (b) and therefore stay on the library by default (a policy, not a
-    fallback; skinny_gemm itself still takes them). None so far: see profiles/decode_gemm/README.md."""
-    return False
+def skinny_gemm_excluded(N, K, w_is_nk, M=None):
+    """(N, K, layout) classes, with the row count where it decides, that lost to the library call plus
+    its elementwise passes and therefore stay on the library by default (a policy, not a fallback;
+    skinny_gemm itself still takes them). tools/bench_decode_gemm.py part (b) excluded none
+    (profiles/decode_gemm/README.md). tools/bench_generate.py part (b) excludes one: the
+    vocabulary-sized [N, K] product of the LM head (N * K >= 2^26 elements; measured at 50,304 x 2048)
+    with all 16 rows, 51.6 us against 50.9 us on matmul_nt. The same shape with 1 and 8 rows wins and
+    stays; 9 - 15 rows were not measured and stay with them (profiles/generate/README.md). ``M`` None
+    asks about the shape alone, which is never excluded as a whole."""
+    return bool(w_is_nk) and M is not None and int(M) >= 16 and int(N) * int(K) >= (1 << 26)
 
 
 def skinny_gemm_why_not(x, w, w_is_nk, bias=None, residual=None):
@@ -1276,9 +1281,10 @@ def skinny_gemm_why_not(x, w, w_is_nk, bias=None, residual=None):
 def skinny_gemm(x, w, w_is_nk, bias=None, act="none", residual=None, nsplit=None, out=None):
     """out[M, N] = act(x[M, K] @ W + bias) + residual on the weight-streaming kernels, M <= 16, fp32
     accumulation and one rounding. ``w`` is [N, K] when ``w_is_nk`` else [K, N]; ``act`` is "none",
-    "gelu" (erf) or "relu". ``nsplit`` None takes skinny_gemm_plan's deterministic split; an explicit
-    value splits K evenly (in multiples of 8) and must leave no split empty. ``out``, if given, is a
-    contiguous, 16-byte aligned [M, N] tensor of x's dtype on x's device that receives the result."""
+    "gelu" (erf), "gelu_tanh" (the tanh approximation, bias_gelu's approximate=True) or "relu".
+    ``nsplit`` None takes skinny_gemm_plan's deterministic split; an explicit value splits K evenly
+    (in multiples of 8) and must leave no split empty. ``out``, if given, is a contiguous, 16-byte
+    aligned [M, N] tensor of x's dtype on x's device that receives the result."""
     fn = "skinny_gemm"
     why = _skinny_reject(x, w, w_is_nk, bias, residual)
     if why is not None:
@@ -1306,3 +1312,173 @@ def skinny_gemm(x, w, w_is_nk, bias=None, act="none", residual=None, nsplit=None
     _check(L.pha_skinny_gemm(_DT[x.dtype], 1 if w_is_nk else 0, _ptr(x), x.stride(0), _ptr(w), _ptr(bias),
                              _ptr(residual), _ptr(out), _ptr(ws), M, N, K, ns, kps, _SKINNY_ACT[act], _stream(x)), fn)
     return out
+
+
+# ----------------------------------------------------------------------------
+# next-token sampling (csrc/kernels/sampling.hip)
+# ----------------------------------------------------------------------------
+SAMPLE_MAX_B = 16   # rows per call: the decode step's batch, as SKINNY_GEMM_MAX_M
+
+
+def _sample_max_v():
+    return 0 if _lib.lib is None else _lib.lib.pha_sample_logits_max_v()
+
+
+SAMPLE_MAX_V = _sample_max_v()   # the kernel's vocabulary limit (0: library not built)
+
+
+def _sample_check(logits, u, temperature, top_k, top_p, finished, out_ids=None, out_logprob=None):
+    """the argument errors of sample_logits, the same on every path (each names its argument)"""
+    fn = "sample_logits"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{fn}: logits must be a 2-D tensor [B, V]")
+    if logits.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise ValueError(f"{fn}: logits are {logits.dtype}; bfloat16, float16 or float32 expected")
+    B, V = logits.shape
+    if B < 1 or B > SAMPLE_MAX_B:
+        raise ValueError(f"{fn}: logits have B={B} rows; 1 to {SAMPLE_MAX_B} expected")
+    if V < 2:
+        raise ValueError(f"{fn}: logits have V={V} columns; at least 2 expected")
+    if logits.stride(1) != 1 or logits.stride(0) < V:
+        raise ValueError(f"{fn}: logits strides {tuple(logits.stride())}: the last must be 1 and the first >= V={V}")
+    dev = logits.device
+    if not isinstance(u, torch.Tensor) or u.dtype != torch.float32 or tuple(u.shape) != (B,) or u.device != dev \
+            or not u.is_contiguous():
+        raise ValueError(f"{fn}: u must be a contiguous float32 [{B}] tensor on {dev}")
+    if not float(temperature) > 0.0:
+        raise ValueError(f"{fn}: temperature={temperature} must be positive")
+    if not (0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"{fn}: top_p={top_p} must be in (0, 1]")
+    if int(top_k) != top_k or not (0 <= int(top_k) <= V):
+        raise ValueError(f"{fn}: top_k={top_k} must be an integer in [0, V={V}]")
+    if finished is not None and (not isinstance(finished, torch.Tensor) or finished.dtype != torch.uint8
+                                 or tuple(finished.shape) != (B,) or finished.device != dev
+                                 or not finished.is_contiguous()):
+        raise ValueError(f"{fn}: finished must be a contiguous uint8 [{B}] tensor on {dev}")
+    for name, t, dt in (("out_ids", out_ids, torch.int64), ("out_logprob", out_logprob, torch.float32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B,)
+                              or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{fn}: {name} must be a contiguous {dt} [{B}] tensor on {dev}")
+
+
+def _sample_reject(logits):
+    """why the kernel cannot take logits that passed _sample_check, or None"""
+    if not logits.is_cuda:
+        return f"logits are on {logits.device}, not a GPU"
+    if logits.dtype not in (torch.bfloat16, torch.float16):
+        return f"logits are {logits.dtype}; the kernel takes bfloat16 or float16"
+    if logits.shape[1] > SAMPLE_MAX_V:
+        return f"V={logits.shape[1]} is above the kernel's {SAMPLE_MAX_V} (one row of keys plus the histograms in LDS)"
+    if logits.data_ptr() % 2:
+        return "logits are not 2-byte aligned"
+    return None
+
+
+def sample_logits_excluded(B, V, top_k, top_p):
+    """(B, V, filter) classes that lost to the composite in tools/bench_generate.py part (a) and stay on
+    it by default (a policy, not a fallback). None: see profiles/generate/README.md."""
+    return False
+
+
+def sample_logits_supported(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None):
+    """what the sampling kernel takes: bf16 / fp16 logits [B, V] on a GPU with 1 <= B <= 16,
+    2 <= V <= SAMPLE_MAX_V (65,536), unit inner stride and a row stride of at least V; float32 u [B];
+    temperature > 0, 0 < top_p <= 1, 0 <= top_k <= V; an optional uint8 finished [B]. float32 logits
+    are not taken (they stay on the composite)."""
+    if _lib.lib is None:
+        return False
+    try:
+        _sample_check(logits, u, temperature, top_k, top_p, finished)
+    except ValueError:
+        return False
+    return _sample_reject(logits) is None and not sample_logits_excluded(logits.shape[0], logits.shape[1], top_k, top_p)
+
+
+def sample_logits_why_not(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None):
+    """the reason the sampling kernel would reject these arguments, for the fallback log"""
+    if _lib.lib is None:
+        return "kernel library not loaded"
+    try:
+        _sample_check(logits, u, temperature, top_k, top_p, finished)
+    except ValueError as e:
+        return str(e)
+    return _sample_reject(logits) or "supported"
+
+
+def _sample_logits_composite(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None, eos_token_id=-1,
+                             pad_token_id=0):
+    """sample_logits' contract in plain torch (any device, any float dtype, any B; no host sync)"""
+    B, V = logits.shape
+    dev = logits.device
+    z = logits.float() / float(temperature)
+    lsm = torch.log_softmax(z, -1)
+    ar = torch.arange(V, device=dev)
+    K = int(top_k) if 0 < int(top_k) < V else V
+    if int(top_k) == 1:
+        ids = torch.where(z == z.max(-1, keepdim=True).values, ar, V).min(-1).values   # lowest index on a tie
+    else:
+        p = torch.exp(lsm)
+        if K < V or float(top_p) < 1.0:
+            _, order = torch.sort(z, dim=-1, descending=True, stable=True)
+            in_k = (ar < K).unsqueeze(0)
+            ps = p.gather(1, order) * in_k
+            keep_sorted = in_k.expand(B, V).clone()
+            if float(top_p) < 1.0:
+                cum = ps.cumsum(-1)
+                keep_sorted &= (cum - ps) < float(top_p) * cum[:, K - 1:K]
+                keep_sorted[:, 0] = True
+            keep = torch.zeros((B, V), dtype=torch.bool, device=dev).scatter_(1, order, keep_sorted)
+            p = p * keep
+        c = p.cumsum(-1)
+        ids = torch.searchsorted(c, u.unsqueeze(1) * c[:, -1:], right=True).squeeze(1).clamp_(max=V - 1)
+    lp = lsm.gather(1, ids.unsqueeze(1)).squeeze(1)
+    if finished is not None:
+        fin = finished.bool()
+        ids = torch.where(fin, int(pad_token_id), ids)
+        lp = torch.where(fin, 0.0, lp)
+        finished.copy_((fin | (ids == int(eos_token_id))).to(torch.uint8))
+    return ids, lp
+
+
+def sample_logits(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None, eos_token_id=-1, pad_token_id=0,
+                  out_ids=None, out_logprob=None):
+    """Next-token ids (int64 [B]) and their log probabilities (fp32 [B]) from ``logits`` [B, V].
+
+    ``p = softmax(logits / temperature)`` in fp32. The order is a stable descending sort by logit
+    (ties: ascending index). ``top_k > 0`` keeps the first ``top_k`` of it; ``top_p < 1`` keeps the
+    shortest prefix of what is left whose renormalised mass is at least ``top_p`` (always one token).
+    The kept set is renormalised and walked in ascending token index; the first token whose running
+    mass exceeds ``u`` (float32 [B] uniforms in [0, 1) from the caller, which makes the call a pure
+    function) is returned. ``top_k == 1`` is greedy: the argmax, the lowest index on a tie, ``u``
+    ignored. The log probability is that of the returned token under the unfiltered softmax.
+    ``finished`` (uint8 [B], updated in place): a row whose flag is set returns ``pad_token_id`` and
+    log probability 0; a row that returns ``eos_token_id`` sets its flag.
+
+    On a GPU, bf16 / fp16 logits with 1 <= B <= 16 and V <= 65,536 (a row's keys and the histograms
+    must fit one workgroup's LDS; ``sample_logits_supported`` is False above) run on one kernel
+    (csrc/kernels/sampling.hip), bitwise reproducible; the row stride may exceed V and elements past V
+    are never read. float32 logits, the CPU and anything else the kernel rejects run the same contract
+    in plain torch (``_sample_logits_composite``; on a GPU recorded as a fallback). PHA_SAMPLE_KERNEL=0
+    forces the composite. ``out_ids`` / ``out_logprob`` receive the results when given."""
+    import os
+    _sample_check(logits, u, temperature, top_k, top_p, finished, out_ids, out_logprob)
+    B, V = logits.shape
+    use = logits.is_cuda and os.environ.get("PHA_SAMPLE_KERNEL", "1") != "0"
+    if use and not sample_logits_excluded(B, V, top_k, top_p):
+        why = "kernel library not loaded" if _lib.lib is None else _sample_reject(logits)
+        if why is None:
+            ids = out_ids if out_ids is not None else torch.empty((B,), dtype=torch.int64, device=logits.device)
+            lp = out_logprob if out_logprob is not None else torch.empty((B,), dtype=torch.float32,
+                                                                         device=logits.device)
+            _check(_L().pha_sample_logits(_DT[logits.dtype], _ptr(logits), logits.stride(0), _ptr(u), _ptr(ids),
+                                          _ptr(lp), _ptr(finished), B, V, float(temperature), int(top_k), float(top_p),
+                                          int(eos_token_id), int(pad_token_id), _stream(logits)), "sample_logits")
+            return ids, lp
+        from . import fallback
+        fallback.note("sample_logits", why + " -> torch composite")
+    ids, lp = _sample_logits_composite(logits, u, temperature, top_k, top_p, finished, eos_token_id, pad_token_id)
+    if out_ids is not None:
+        ids = out_ids.copy_(ids)
+    if out_logprob is not None:
+        lp = out_logprob.copy_(lp)
+    return ids, lp
