@@ -22,6 +22,13 @@
 // (no host sync, graph-capturable). Both kernels range-check the value before any address is
 // formed from it: out of range, the partial kernel touches nothing and the combine kernel fills
 // `out` with NaN.
+//
+// Per-row form (pha_decode_attn_rows): `ts_dev` is an int32 device array [B] and batch row b uses
+// ts_dev[b], so prompts of different lengths decode in one launch and every row streams only its
+// own live keys. The grid is the same; each workgroup of (split, head, b) reads its row's step,
+// range-checks it on its own (a bad row touches nothing and gets NaN, the others are unaffected)
+// and depends on no other row. ROWS is a template parameter: the scalar instantiation is the code
+// it was before.
 #include "common.h"
 
 namespace pha {
@@ -45,7 +52,7 @@ __device__ __forceinline__ void osm_merge(float& m, float& l, float (&o)[8], flo
 }
 
 // ws: [B, H, nsplit, D + 2] fp32 rows of (o[D], m, l)
-template <typename T, int D>
+template <typename T, int D, bool ROWS>
 __global__ __launch_bounds__(DECODE_ATTN_THREADS) void decode_attn_partial(
     const T* __restrict__ qkv, const T* __restrict__ qkv_bias, T* __restrict__ cache,
     const float* __restrict__ mask, long mask_sb, long mask_sh, float scale, int ts_host,
@@ -56,7 +63,7 @@ __global__ __launch_bounds__(DECODE_ATTN_THREADS) void decode_attn_partial(
   constexpr int U = (G * 4 <= DECODE_ATTN_CHUNK) ? 4 : (DECODE_ATTN_CHUNK / G);   // keys in flight per group
   static_assert(U >= 1 && DECODE_ATTN_CHUNK % (G * U) == 0, "chunk must be whole passes of the workgroup");
 
-  const int ts = ts_dev ? *ts_dev : ts_host;
+  const int ts = ROWS ? ts_dev[blockIdx.z] : (ts_dev ? *ts_dev : ts_host);   // ROWS: ts_dev is [B]
   if (ts < 0 || ts >= max_seq) return;             // nothing is read or written with a bad time step
   const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int k0 = s * DECODE_ATTN_CHUNK;
@@ -207,12 +214,12 @@ __global__ __launch_bounds__(DECODE_ATTN_THREADS) void decode_attn_partial(
 }
 
 // one thread per element of D; out: [B, H * D]
-template <typename T>
+template <typename T, bool ROWS>
 __global__ void decode_attn_combine(const float* __restrict__ ws, T* __restrict__ out, int ts_host,
                                     const int* __restrict__ ts_dev, int H, int D, int max_seq, int nsplit) {
   const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
   const size_t bh = (size_t)b * H + h;
-  const int ts = ts_dev ? *ts_dev : ts_host;
+  const int ts = ROWS ? ts_dev[b] : (ts_dev ? *ts_dev : ts_host);
   if (ts < 0 || ts >= max_seq) {
     Cvt<T>::st(out, bh * D + d, __builtin_nanf(""));
     return;
@@ -232,21 +239,20 @@ __global__ void decode_attn_combine(const float* __restrict__ ws, T* __restrict_
   Cvt<T>::st(out, bh * D + d, L > 0.f ? acc / L : 0.f);   // every key masked out: zeros
 }
 
-template <typename T>
+template <typename T, bool ROWS>
 static int decode_attn_launch(const void* qkv, const void* bias, void* cache, const float* mask, long msb, long msh,
                               float scale, int ts, const int* ts_dev, void* out, float* ws, int B, int H, int D,
                               int max_seq, hipStream_t st) {
   const int nsplit = (max_seq + DECODE_ATTN_CHUNK - 1) / DECODE_ATTN_CHUNK;
   const dim3 grid(nsplit, H, B);
-#define PHA_DA_LAUNCH(DD)                                                                                         \
-  decode_attn_partial<T, DD><<<grid, DECODE_ATTN_THREADS, 0, st>>>((const T*)qkv, (const T*)bias, (T*)cache, mask, \
-                                                                   msb, msh, scale, ts, ts_dev, ws, B, H, max_seq, \
-                                                                   nsplit)
+#define PHA_DA_LAUNCH(DD)                                                                                \
+  decode_attn_partial<T, DD, ROWS><<<grid, DECODE_ATTN_THREADS, 0, st>>>(                                \
+      (const T*)qkv, (const T*)bias, (T*)cache, mask, msb, msh, scale, ts, ts_dev, ws, B, H, max_seq, nsplit)
   if (D == 32) PHA_DA_LAUNCH(32);
   else if (D == 64) PHA_DA_LAUNCH(64);
   else PHA_DA_LAUNCH(128);
 #undef PHA_DA_LAUNCH
-  decode_attn_combine<T><<<dim3(H, B), D, 0, st>>>(ws, (T*)out, ts, ts_dev, H, D, max_seq, nsplit);
+  decode_attn_combine<T, ROWS><<<dim3(H, B), D, 0, st>>>(ws, (T*)out, ts, ts_dev, H, D, max_seq, nsplit);
   return (int)hipGetLastError();
 }
 
@@ -264,10 +270,26 @@ PHA_API int pha_decode_attn(int dt, const void* qkv, const void* qkv_bias, void*
     return (int)hipErrorInvalidValue;
   if (!ts_dev && (ts < 0 || ts >= max_seq)) return (int)hipErrorInvalidValue;
   if (dt == pha::kBF16)
-    return pha::decode_attn_launch<pha::bf16_t>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts, ts_dev, out,
+    return pha::decode_attn_launch<pha::bf16_t, false>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts, ts_dev, out,
                                                 ws, B, H, D, max_seq, stream);
   if (dt == pha::kF16)
-    return pha::decode_attn_launch<pha::half_t>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts, ts_dev, out,
+    return pha::decode_attn_launch<pha::half_t, false>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts, ts_dev, out,
                                                 ws, B, H, D, max_seq, stream);
+  return (int)hipErrorInvalidValue;
+}
+
+// The per-row form: as pha_decode_attn, with `ts_rows` a device int32 array [B] (never null) whose
+// element b is the time step of batch row b.
+PHA_API int pha_decode_attn_rows(int dt, const void* qkv, const void* qkv_bias, void* cache, const float* mask,
+                                 long mask_sb, long mask_sh, float scale, const int* ts_rows, void* out, float* ws,
+                                 int B, int H, int D, int max_seq, hipStream_t stream) {
+  if (B <= 0 || H <= 0 || max_seq <= 0 || B > 65535 || H > 65535 || (D != 32 && D != 64 && D != 128) || !ts_rows)
+    return (int)hipErrorInvalidValue;
+  if (dt == pha::kBF16)
+    return pha::decode_attn_launch<pha::bf16_t, true>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0, ts_rows,
+                                                      out, ws, B, H, D, max_seq, stream);
+  if (dt == pha::kF16)
+    return pha::decode_attn_launch<pha::half_t, true>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0, ts_rows,
+                                                      out, ws, B, H, D, max_seq, stream);
   return (int)hipErrorInvalidValue;
 }

@@ -241,6 +241,39 @@ def _decode_kernel_ok(qkv, cache, mask, device_time_step, dropout_rate, training
     return False
 
 
+def _decode_rows_composite(q, k, v, c, ts_rows, mask, dropout_rate, training, mode):
+    """the decode stage's attention with a step per batch row, on the composite: q / k / v [B, H, 1, D]
+    of the new token, ``c`` the layer's [2, B, H, max_seq, D] cache, ``ts_rows`` int32 [B] on the
+    cache's device. Row b appends at ts_rows[b] and attends over [0, ts_rows[b]]. Keys and values
+    above a row's step are replaced by zeros before the products (an additive -inf would leave a NaN
+    score NaN), so the result does not depend on what the cache holds there. On the GPU the key
+    dimension is the whole cache: the host never learns max(ts_rows). As in the kernels, a row whose
+    step is outside the cache leaves it alone and gets NaN."""
+    B, max_seq = c.shape[1], c.shape[3]
+    idx = ts_rows.reshape(-1).long()
+    ok = ((idx >= 0) & (idx < max_seq))[:, None, None]
+    idx = idx.clamp(0, max_seq - 1)
+    rows = torch.arange(B, device=c.device)
+    c[0][rows, :, idx] = torch.where(ok, k[:, :, 0], c[0][rows, :, idx])
+    c[1][rows, :, idx] = torch.where(ok, v[:, :, 0], c[1][rows, :, idx])
+    q = torch.where(ok[..., None], q, torch.full((), float("nan"), dtype=q.dtype, device=q.device))
+    L = max_seq if c.is_cuda else min(max_seq, int(idx.max()) + 1)
+    live = torch.arange(L, device=c.device)[None, :] <= idx[:, None]             # [B, L]
+    zero = torch.zeros((), dtype=c.dtype, device=c.device)
+    kk = torch.where(live[:, None, :, None], c[0, :, :, :L], zero)
+    vv = torch.where(live[:, None, :, None], c[1, :, :, :L], zero)
+    m = torch.zeros(B, 1, 1, L, dtype=torch.float32, device=c.device).masked_fill_(~live[:, None, None, :],
+                                                                                   float("-inf"))
+    if mask is not None:
+        um = mask
+        if um.dtype == torch.bool:
+            um = torch.zeros(um.shape, dtype=torch.float32, device=um.device).masked_fill_(~um, float("-inf"))
+        if um.shape[-1] != 1:
+            um = um[..., :L]
+        m = m + um.to(device=c.device, dtype=torch.float32)
+    return _attention(q, kk, vv, m.to(q.dtype), dropout_rate, training, mode, causal=False)
+
+
 def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, linear_weights, linear_biases,
                             ffn_ln_scales, ffn_ln_biases, ffn1_weights, ffn1_biases, ffn2_weights, ffn2_biases,
                             pre_layer_norm=True, epsilon=1e-05, cache_kvs=None, time_step=None, attn_mask=None,
@@ -253,6 +286,10 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     decode stage's bias add, cache append and attention are one split-KV kernel pair
     (csrc/kernels/decode_attn.hip); with ``time_step`` an int32 device tensor that step reads it on
     the device, so it neither syncs the host nor changes shape and can be captured in a hipGraph.
+    ``time_step`` may also be an int32 tensor of B elements (B > 1; on the GPU a device tensor, on the
+    CPU a CPU tensor): batch row b then writes position ``time_step[b]`` and attends over
+    [0, time_step[b]], whatever the cache holds above it, on the kernel pair and on the composite
+    alike and without a host sync, so right-padded prompts of different lengths decode in one batch.
     PHA_DECODE_ATTN=0 keeps the composite. With at most 16 rows (B * S <= 16) and no gradient the four
     products of each layer run on the weight-streaming kernels (csrc/kernels/skinny_gemm.hip): QKV in
     either ``trans_qkvw`` layout without a transposed copy, the output projection and ffn2 with bias
@@ -261,10 +298,18 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     PHA_DECODE_GEMM=0 keeps the library GEMMs and the separate elementwise passes."""
     h = _u(x)
     B, S, E = h.shape
-    ts = ts_dev = None
+    ts = ts_dev = ts_rows = None
     if time_step is not None:
         t = _u(time_step)
-        if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.numel() == 1:
+        if isinstance(t, torch.Tensor) and t.numel() > 1:
+            # a step per batch row, on the device the layers run on; never read on the host
+            if t.dtype != torch.int32 or t.numel() != B or t.device != h.device or S != 1 or cache_kvs is None:
+                raise ValueError(f"fused_multi_transformer: a time_step of more than one element must be int32 [{B}] "
+                                 f"on {h.device} in the decode stage, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            ts_rows = t.reshape(-1).contiguous()
+            if t.is_cuda:
+                ts_dev = ts_rows
+        elif isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.numel() == 1:
             ts_dev = t   # read by the decode kernel on the device; .item() only if a layer cannot use it
         else:
             ts = int(t.reshape(-1)[0].item()) if isinstance(t, torch.Tensor) else int(t)
@@ -293,7 +338,8 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             # attention path first: the decode kernels add the QKV bias themselves, anywhere else it
             # goes into this product's epilogue
             use_decode = decode and _decode_kernel_ok(a2.as_strided((B, 3, H, D), (0, 0, 0, 0)), _u(cache_kvs[i]), mask,
-                                                      ts_dev is not None, dropout_rate, training)
+                                                      ts_dev if ts_dev is not None else False, dropout_rate,
+                                                      training)
             qbe = None if use_decode or qb is None else qb.reshape(-1)
             if qbe is not None and not _ops.hip.skinny_gemm_supported(a2, w2, trans_qkvw, qbe):
                 qbe = None   # added below as today
@@ -303,7 +349,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         else:
             qkv = a2 @ (w2.t() if trans_qkvw else w2)
             use_decode = decode and _decode_kernel_ok(qkv.reshape(B, 3, H, D), _u(cache_kvs[i]), mask,
-                                                      ts_dev is not None, dropout_rate, training)
+                                                      ts_dev if ts_dev is not None else False, dropout_rate, training)
         if use_decode:
             # one split-KV kernel pair: bias add, cache append and attention over [0, time_step]
             if qb is not None and (qb.dtype != qkv.dtype or not qb.is_contiguous()):
@@ -311,14 +357,16 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             o = _ops.hip.decode_attention(qkv.reshape(B, 3, H, D), None if qb is None else qb.reshape(3, H, D),
                                           _u(cache_kvs[i]), ts_dev if ts_dev is not None else ts, mask)
         else:
-            if ts_dev is not None and ts is None:
+            if ts_dev is not None and ts is None and ts_rows is None:
                 ts = int(ts_dev.item())
             if qb is not None:
                 qkv = qkv + qb.reshape(-1)
             qkv = qkv.reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
             q, k, v = qkv[0], qkv[1], qkv[2]
             causal = False
-            if cache_kvs is not None:
+            if ts_rows is not None:
+                o = _decode_rows_composite(q, k, v, _u(cache_kvs[i]), ts_rows, mask, dropout_rate, training, mode)
+            elif cache_kvs is not None:
                 c = _u(cache_kvs[i])
                 if ts is None:
                     c[0, :, :, :S] = k
@@ -328,10 +376,11 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                     c[0, :, :, ts:ts + S] = k
                     c[1, :, :, ts:ts + S] = v
                     k, v = c[0, :, :, :ts + S], c[1, :, :, :ts + S]
-            m = mask
-            if m is not None and m.shape[-1] != k.shape[2]:
-                m = m[..., :k.shape[2]]
-            o = _attention(q, k, v, m, dropout_rate, training, mode, causal=causal and S > 1)
+            if ts_rows is None:
+                m = mask
+                if m is not None and m.shape[-1] != k.shape[2]:
+                    m = m[..., :k.shape[2]]
+                o = _attention(q, k, v, m, dropout_rate, training, mode, causal=causal and S > 1)
             o = o.transpose(1, 2).reshape(B, S, H * D)
         lw, lb = _u(linear_weights[i]), _u(linear_biases[i]) if linear_biases is not None else None
         o2 = _skinny_linear(o, lw, lb, "none", residual if epi else None) if skinny else None

@@ -271,7 +271,8 @@ class GPTForPretraining(nn.Layer):
 
     def generate(self, input_ids, max_new_tokens, **kwargs):
         """cached generation (greedy search or temperature / top-k / top-p sampling) with a KV cache:
-        ``models.gpt_generate.GPTGenerator.generate`` on a generator kept with the model"""
+        ``models.gpt_generate.GPTGenerator.generate`` on a generator kept with the model. Prompts of
+        different lengths go in as one padded batch with ``seq_lens`` or ``attention_mask``."""
         gen = self.__dict__.get("_generator")
         if gen is None:
             from .gpt_generate import GPTGenerator

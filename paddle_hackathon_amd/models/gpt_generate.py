@@ -13,6 +13,12 @@ preallocated ``[2, B, H, prompt + max_new, D]`` key / value caches, and every fu
 with nothing in the step that syncs the host, so on the GPU the whole step is captured once in a
 hipGraph and replayed per token.
 
+Prompts of different lengths (``seq_lens`` or ``attention_mask``) are right-padded to the longest:
+under causal attention the padding cannot reach a real position, so the prefill runs unmasked, row
+b takes its first token from position ``len_b - 1`` and then decodes with a time step of its own,
+``time_step`` being int32 ``[B]``. It overwrites the stale padding rows of its cache as it goes and
+never reads a key above its step, so a step streams the live keys of every row and no padding.
+
 The model's own parameters are used: ``nn.Linear`` weights are ``[in, out]``, the ``[K, N]`` layout
 of the kernels, and go in as views. The one exception is the fused QKV projection, whose outputs are
 ordered (head, 3, D) while the decode kernels need (3, head, D): the generator keeps one repacked
@@ -37,11 +43,11 @@ EOS_CHECK_EVERY = 16   # decode steps between two host reads of finished.all()
 class _GraphState:
     """the static buffers of one captured decode step, and the graph once it exists"""
 
-    def __init__(self, B, cache_len, cfg, dtype, device):
+    def __init__(self, B, cache_len, cfg, dtype, device, ragged=False):
         H, D = cfg.num_heads, cfg.head_dim
         self.caches = [torch.zeros(2, B, H, cache_len, D, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
         self.tok = torch.zeros(B, dtype=torch.int64, device=device)
-        self.ts = torch.zeros(1, dtype=torch.int32, device=device)
+        self.ts = torch.zeros(B if ragged else 1, dtype=torch.int32, device=device)   # ragged: a step per row
         self.u = torch.zeros(B, dtype=torch.float32, device=device)
         self.finished = torch.zeros(B, dtype=torch.uint8, device=device)
         self.ids = self.logprob = None
@@ -55,7 +61,7 @@ class GPTGenerator:
     def __init__(self, model):
         self.model = model
         self._qkv = {}        # layer index -> (weight version, bias version, repacked weight, repacked bias)
-        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad) -> _GraphState
+        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged) -> _GraphState
         self._eager = set()   # keys whose warm-up step left the kernel path: not tried again
         self.captures = 0     # hipGraph captures so far (a second generate call adds none)
         self.last_caches = None
@@ -134,10 +140,51 @@ class GPTGenerator:
         st.ts.add_(1)
         return ids, lp
 
+    # ------------------------------------------------------------------------------ prompts
+    @staticmethod
+    def _prompt_lens(ids_in, seq_lens, attention_mask):
+        """(ids, lens): the prompts right-padded, trailing columns that are padding in every row
+        dropped, and the B prompt lengths as Python ints; lens is None where neither argument is given.
+        Reads the host once."""
+        B, P = ids_in.shape
+        if seq_lens is not None and attention_mask is not None:
+            raise ValueError("generate: give seq_lens or attention_mask, not both")
+        if seq_lens is None and attention_mask is None:
+            return ids_in, None
+        if seq_lens is not None:
+            t = seq_lens._t if isinstance(seq_lens, Tensor) else torch.as_tensor(seq_lens)
+            if t.dim() != 1 or t.shape[0] != B or t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError(f"generate: seq_lens must be {B} ints, got {t.dtype} {tuple(t.shape)}")
+            lens = [int(v) for v in t.tolist()]
+            if min(lens) < 1 or max(lens) > P:
+                raise ValueError(f"generate: every seq_lens entry must be in [1, {P}], got {lens}")
+            return ids_in[:, :max(lens)], lens
+        m = attention_mask._t if isinstance(attention_mask, Tensor) else torch.as_tensor(attention_mask)
+        if tuple(m.shape) != (B, P):
+            raise ValueError(f"generate: attention_mask must be [{B}, {P}], got {tuple(m.shape)}")
+        m = m.cpu()
+        if not bool(((m == 0) | (m == 1)).all()):
+            raise ValueError("generate: attention_mask must be bool or 0 / 1")
+        m = m != 0
+        lens = [int(v) for v in m.sum(1).tolist()]
+        first = m.int().argmax(1).tolist()   # column of the first one
+        if min(lens) < 1:
+            raise ValueError("generate: attention_mask has a row without a token")
+        for b in range(B):
+            if not bool(m[b, first[b]:first[b] + lens[b]].all()):
+                raise ValueError(f"generate: attention_mask row {b} is not one contiguous run of ones")
+            if first[b] != 0 and first[b] + lens[b] != P:
+                raise ValueError(f"generate: attention_mask row {b} is neither right-padded (the run starts at column "
+                                 f"0) nor left-padded (it ends at column {P - 1})")
+        if any(first):   # left-padded rows move to the left edge: one gather
+            col = torch.arange(P)[None, :] + torch.tensor(first)[:, None]
+            ids_in = ids_in.gather(1, col.clamp_(max=P - 1).to(ids_in.device))
+        return ids_in[:, :max(lens)], lens
+
     # ------------------------------------------------------------------------------ generate
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, decode_strategy="greedy_search", temperature=1.0, top_k=0, top_p=1.0,
-                 eos_token_id=None, pad_token_id=0, seed=None, use_graph=None):
+                 eos_token_id=None, pad_token_id=0, seed=None, use_graph=None, seq_lens=None, attention_mask=None):
         """``max_new_tokens`` tokens after ``input_ids`` [B, prompt]: (ids int64 [B, max_new_tokens],
         scores fp32 [B, max_new_tokens]), the score being the log probability of the token under the
         temperature-scaled, unfiltered softmax (0 at padded positions).
@@ -149,15 +196,27 @@ class GPTGenerator:
         With ``eos_token_id`` a row that emits it is padded with ``pad_token_id`` from then on, and the
         loop reads ``finished.all()`` every 16 steps to stop early; nothing else syncs the host.
 
-        All prompts have one length: padded prompts and ``attention_mask`` are not supported. The
-        model must be in eval mode with ``tensor_parallel_degree == 1``, and
-        ``prompt + max_new_tokens <= max_position_embeddings``.
+        Prompts of different lengths are given by one of two arguments. ``seq_lens`` (B ints or an
+        int tensor): row b's prompt is ``input_ids[b, :seq_lens[b]]`` with 1 <= seq_lens[b] <= prompt, the
+        rest is ignored. ``attention_mask`` ([B, prompt], bool or 0 / 1): every row is one non-empty
+        contiguous run of ones that starts at column 0 (right-padded) or ends at the last column
+        (left-padded; such rows are shifted to the left edge by one gather). Anything else is a
+        ``ValueError``; the check reads the host once, before the loop. Row b of the output continues
+        its own prompt: the prefill runs unmasked over the longest prompt (causal, so padding reaches
+        no real position), the first token comes from position ``len_b - 1`` and the decode steps run
+        with a time step per row, reading no padding. Without either argument, or with all lengths
+        equal, the call is the uniform one, bit for bit.
+
+        The model must be in eval mode with ``tensor_parallel_degree == 1``, and
+        ``longest prompt + max_new_tokens <= max_position_embeddings``.
 
         ``use_graph`` None captures the decode step in one hipGraph when the model is on the GPU and
         a warm-up step took the kernel path everywhere (no recorded fallback, device-side time step);
         True insists on it, False runs the same step eagerly. The graph and its static buffers are kept
-        on the generator per (B, cache length, strategy, temperature, top_k, top_p, eos, pad), KV caches
-        included; ``GPTGenerator.clear()`` releases them."""
+        on the generator per (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged), KV
+        caches included; ``GPTGenerator.clear()`` releases them. The prompt lengths are data of the
+        ragged graph, not part of its key: one capture serves every mix of lengths with the same
+        longest prompt."""
         model, cfg = self.model, self.model.cfg
         if cfg.tensor_parallel_degree != 1:
             raise ValueError("generate: tensor_parallel_degree must be 1")
@@ -168,7 +227,10 @@ class GPTGenerator:
         ids_in = input_ids._t if isinstance(input_ids, Tensor) else torch.as_tensor(input_ids)
         if ids_in.dim() != 2 or ids_in.shape[0] < 1 or ids_in.shape[1] < 1:
             raise ValueError(f"generate: input_ids must be [B, prompt], got {tuple(ids_in.shape)}")
-        B, P = ids_in.shape
+        B = ids_in.shape[0]
+        ids_in, lens = self._prompt_lens(ids_in, seq_lens, attention_mask)
+        P = ids_in.shape[1]   # the longest prompt
+        ragged = lens is not None and min(lens) != P
         n_new = int(max_new_tokens)
         if n_new < 1:
             raise ValueError(f"generate: max_new_tokens={max_new_tokens} must be at least 1")
@@ -183,13 +245,13 @@ class GPTGenerator:
         if use_graph and not wte.is_cuda:
             raise RuntimeError("generate: use_graph=True needs the model on a GPU")
         cache_len = P + n_new
-        key = (B, cache_len, s["strategy"], s["temperature"], s["top_k"], s["top_p"], s["eos"], s["pad"])
+        key = (B, cache_len, s["strategy"], s["temperature"], s["top_k"], s["top_p"], s["eos"], s["pad"], ragged)
         weights = self._layer_weights()
         want_graph = wte.is_cuda and use_graph is not False and n_new > 1 \
             and (bool(use_graph) or key not in self._eager)
         st = self._graphs.get(key) if want_graph else None
         if st is None:
-            st = _GraphState(B, cache_len, cfg, dtype, dev)
+            st = _GraphState(B, cache_len, cfg, dtype, dev, ragged)
         else:
             for c in st.caches:
                 c.zero_()
@@ -206,21 +268,28 @@ class GPTGenerator:
         out_lp = torch.zeros((B, n_new), dtype=torch.float32, device=dev)
 
         # prefill: the context stage fills the caches; the first token comes from the last position
+        # (of each row's own prompt where the lengths differ)
         x = model.gpt.embeddings(_wrap(ids_in))._t
         h = self._stack(x, weights, st.caches)
-        ids, lp = self._sample(self._logits(h[:, -1].contiguous()), U[0].contiguous(), st.finished, s)
+        if ragged:
+            ts0 = torch.tensor(lens, dtype=torch.int32).to(dev)
+            last = h[torch.arange(B, device=dev), ts0.long() - 1]
+        else:
+            ts0, last = P, h[:, -1]
+        ids, lp = self._sample(self._logits(last.contiguous()), U[0].contiguous(), st.finished, s)
         out_ids[:, 0], out_lp[:, 0] = ids, lp
         st.tok.copy_(ids)
-        st.ts.fill_(P)
+        self._set_ts(st, ts0)
 
         graph = None
         if want_graph:
-            graph = self._graph_for(st, weights, s, P, required=bool(use_graph))
+            graph = self._graph_for(st, weights, s, ts0, required=bool(use_graph))
             if graph is not None:
                 self._graphs[key] = st
             else:
                 self._eager.add(key)
-        host_ts = None if wte.is_cuda else P   # on the CPU the composite takes the step as a Python int
+        # on the CPU the composite takes a uniform step as a Python int (per-row steps stay a tensor)
+        host_ts = None if wte.is_cuda or ragged else P
         self.last_steps = 0
         for j in range(1, n_new):
             self.last_steps = j
@@ -237,7 +306,15 @@ class GPTGenerator:
                 break
         return _wrap(out_ids), _wrap(out_lp)
 
-    def _graph_for(self, st, weights, s, P, required):
+    @staticmethod
+    def _set_ts(st, ts0):
+        """the first decode step: the prompt length, or the int32 [B] lengths of a ragged call"""
+        if isinstance(ts0, torch.Tensor):
+            st.ts.copy_(ts0)
+        else:
+            st.ts.fill_(ts0)
+
+    def _graph_for(self, st, weights, s, ts0, required):
         """the captured step of ``st`` (captured now if it is new or the weights moved), or None where
         the warm-up step shows that a piece of it left the kernel path and the graph was not required"""
         at = tuple(t.data_ptr() for group in weights for t in group)
@@ -246,21 +323,24 @@ class GPTGenerator:
         from ..ops import fallback
         keep = (st.tok.clone(), st.finished.clone())
         before = fallback.total()
-        self._step(weights, st, s)   # warm-up: what it appends at position P is rewritten by the first replay
+        self._step(weights, st, s)   # warm-up: what it appends at the first step is rewritten by the first replay
         clean = fallback.total() == before and os.environ.get("PHA_DECODE_ATTN", "1") != "0" \
             and st.caches[0].dtype in (torch.bfloat16, torch.float16) and self.model.cfg.head_dim in (32, 64, 128)
         st.tok.copy_(keep[0])
         st.finished.copy_(keep[1])
-        st.ts.fill_(P)
+        self._set_ts(st, ts0)
         if not clean and not required:
             for c in st.caches:
-                c[:, :, :, P].zero_()
+                if isinstance(ts0, torch.Tensor):
+                    c[:, torch.arange(c.shape[1], device=c.device), :, ts0.long()] = 0
+                else:
+                    c[:, :, :, ts0].zero_()
             return None
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             st.ids, st.logprob = self._step(weights, st, s)
         self.captures += 1
-        st.ts.fill_(P)   # capture launches nothing: the first replay is step 0
+        self._set_ts(st, ts0)   # capture launches nothing: the first replay is step 0
         st.graph, st.weights_at = g, at
         return g

@@ -40,6 +40,7 @@ SIGNATURES = {
     # decode_attn.hip
     "pha_decode_attn_chunk": (I, []),
     "pha_decode_attn": (I, [I, P, P, P, P, LG, LG, F, I, P, P, P, I, I, I, I, P]),
+    "pha_decode_attn_rows": (I, [I, P, P, P, P, LG, LG, F, P, P, P, I, I, I, I, P]),
     # flash_attn.hip
     "pha_flash_attn_fwd_ext": (I, [I, P, P, P, P, P, I, I, I, I, I, I, F, I, P, LG, LG, LG, F, U, P, P]),
     "pha_flash_attn_bwd_ext": (I, [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P, LG, LG, LG, F, U, P, LG,

@@ -1094,7 +1094,9 @@ def decode_attn_supported(qkv, cache, mask=None, device_time_step=False):
     """what the decode kernel takes: a bf16 / fp16 [B, 3, H, D] QKV product with D in 32 / 64 / 128,
     a [2, B, H, max_seq, D] cache of the same dtype and device, and an optional additive / boolean
     mask broadcastable to [B, H, 1, keys] that needs no gradient (with a device time step its key
-    dimension must span the whole cache, or be 1)"""
+    dimension must span the whole cache, or be 1). ``device_time_step`` is a bool or the time-step
+    tensor itself, which is then checked too: int32, on the device of ``qkv``, one element (one step
+    for the batch) or B elements (a step per batch row)"""
     if not DECODE_ATTN_CHUNK:
         return False
     if not (isinstance(qkv, torch.Tensor) and isinstance(cache, torch.Tensor) and qkv.is_cuda and cache.is_cuda):
@@ -1106,6 +1108,11 @@ def decode_attn_supported(qkv, cache, mask=None, device_time_step=False):
     B, _, H, D = qkv.shape
     if D not in (32, 64, 128) or B < 1 or H < 1 or B > 65535 or H > 65535:
         return False
+    if isinstance(device_time_step, torch.Tensor):
+        t = device_time_step
+        if t.dtype != torch.int32 or t.device != qkv.device or t.numel() not in (1, B) or not t.is_contiguous():
+            return False
+        device_time_step = True
     if tuple(cache.shape[:3]) != (2, B, H) or cache.shape[4] != D or cache.shape[3] < 1 or not cache.is_contiguous():
         return False
     if mask is not None:
@@ -1146,9 +1153,17 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
     QKV product of the new token and ``qkv_bias`` [3, H, D] (or None) its bias; the biased key and
     value are written to ``cache`` [2, B, H, max_seq, D] at ``time_step`` in place, and the biased,
     scaled query attends over the positions [0, time_step]. ``time_step`` is a Python int (checked
-    here) or an int32 device tensor of one element read by the kernels (no host sync; out of range,
-    the cache is left alone and the output is NaN). Returns [B, 1, H * D]."""
+    here) or an int32 device tensor read by the kernels (no host sync; out of range, the cache is
+    left alone and the output is NaN): one element is the step of the whole batch, B elements give
+    batch row b its own step ``time_step[b]`` (row b appends at it and reads no key above it; a row
+    out of range is left alone and gets NaN, the others are unaffected). At B == 1 the two forms
+    coincide. Returns [B, 1, H * D]."""
     fn = "decode_attention"
+    if isinstance(time_step, torch.Tensor) and isinstance(qkv, torch.Tensor) and qkv.dim() == 4:
+        if time_step.dtype != torch.int32 or time_step.device != qkv.device \
+                or time_step.numel() not in (1, qkv.shape[0]) or not time_step.is_contiguous():
+            raise ValueError(f"{fn}: a tensor time_step must be contiguous int32 on {qkv.device} with one element "
+                             f"or one per batch row ({qkv.shape[0]})")
     if not decode_attn_supported(qkv, cache, mask, isinstance(time_step, torch.Tensor)):
         raise ValueError(f"{fn}: unsupported arguments (see decode_attn_supported)")
     B, _, H, D = qkv.shape
@@ -1162,9 +1177,7 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
             raise ValueError(f"{fn}: qkv_bias must be a contiguous {qkv.dtype} [3, {H}, {D}] tensor on {dev}")
     ts, ts_dev = 0, None
     if isinstance(time_step, torch.Tensor):
-        if time_step.dtype != torch.int32 or time_step.device != dev or time_step.numel() != 1:
-            raise ValueError(f"{fn}: a tensor time_step must be one int32 element on {dev}")
-        ts_dev = time_step
+        ts_dev = time_step   # checked above
     else:
         ts = int(time_step)
         if ts < 0 or ts >= max_seq:
@@ -1179,6 +1192,10 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
     ws = torch.empty((B, H, nsplit, D + 2), dtype=torch.float32, device=dev)
     out = torch.empty((B, 1, H * D), dtype=qkv.dtype, device=dev)
     sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(D))
+    if ts_dev is not None and ts_dev.numel() > 1:   # a step per batch row
+        _check(_L().pha_decode_attn_rows(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc,
+                                         _ptr(ts_dev), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
+        return out
     _check(_L().pha_decode_attn(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc, ts,
                                 _ptr(ts_dev), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
     return out

@@ -11,9 +11,19 @@ against the composite that PHA_DECODE_ATTN=0 keeps.
     ts = 1023: eager on both paths (host int time step), eager with a device time step, and the
     new path replayed from one captured graph.
 
+(c) with --rows: the time step per batch row (an int32 [B] tensor, pha_decode_attn_rows) at the shapes
+    of (a), every arm one captured graph over the 24 caches. The scalar device-step call of this tree
+    against the per-row call with B equal steps and, with --parent-lib NAME, against pha_decode_attn
+    of a library built from the parent commit's decode_attn.hip (a file name under
+    paddle_hackathon_amd/_C/); then eight steps spread evenly over 128..2047 against all eight at 2047.
+    "within" is the project's gating rule: the medians differ by no more than the larger min - max
+    spread of the two arms.
+
 Prints markdown tables. Usage: python tools/bench_decode_attn.py [--rounds 7] [--iters 960] [--skip-model]
+                                                                 [--rows [--parent-lib NAME] [--skip-attention]]
 """
 import argparse
+import ctypes
 import os
 import statistics
 import sys
@@ -21,7 +31,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from paddle_hackathon_amd.ops import hip  # noqa: E402
+from paddle_hackathon_amd.ops import hip, _abi, _lib  # noqa: E402
 from paddle_hackathon_amd.incubate.nn import functional as FF  # noqa: E402
 
 COPY_TBS = 6.29   # measured float4 copy rate of the MI355X (HBM3E), TB/s
@@ -105,6 +115,93 @@ def bench_attention(rounds, iters):
     print()
 
 
+def bench_rows(rounds, iters, parent_lib):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    qkv = torch.randn(B, 3, H, D, device="cuda", generator=g).bfloat16()
+    qb = (torch.randn(3, H, D, device="cuda", generator=g) * 0.1).bfloat16()
+    caches = [torch.randn(2, B, H, MAX_SEQ, D, device="cuda", generator=g).bfloat16() for _ in range(LAYERS)]
+    reps = max(4, iters // LAYERS)
+
+    def us(t):
+        return f"{t[0] * 1e3 / LAYERS:.2f} ({t[1] * 1e3 / LAYERS:.2f} - {t[2] * 1e3 / LAYERS:.2f})"
+
+    def within(a, b):
+        margin = max(a[2] - a[1], b[2] - b[1])
+        d = (a[0] - b[0]) * 1e3 / LAYERS
+        return f"{d:+.2f} us, margin {margin * 1e3 / LAYERS:.2f}: " + ("within" if abs(a[0] - b[0]) <= margin else
+                                                                         "slower" if d > 0 else "faster")
+
+    def capture(fn):
+        fn(0)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(LAYERS):
+                fn(i)
+        return gr
+
+    def raw(L):
+        """pha_decode_attn of library L called directly, on one workspace and output of its own: the two
+        libraries' arms then differ in nothing but the library"""
+        nsplit = -(-MAX_SEQ // hip.DECODE_ATTN_CHUNK)
+        ws = torch.empty(B, H, nsplit, D + 2, dtype=torch.float32, device="cuda")
+        out = torch.empty(B, 1, H * D, dtype=torch.bfloat16, device="cuda")
+
+        def call(cache, ts_dev):
+            _abi.check(L.pha_decode_attn(_abi.DT[qkv.dtype], qkv.data_ptr(), qb.data_ptr(), cache.data_ptr(), None, 0, 0,
+                                         D ** -0.5, 0, ts_dev.data_ptr(), out.data_ptr(), ws.data_ptr(), B, H, D,
+                                         MAX_SEQ, _abi.stream(qkv)), "pha_decode_attn")
+            return out
+        return call
+
+    parent = tree = None
+    if parent_lib:
+        L = ctypes.CDLL(os.path.join(os.path.dirname(_lib.LIB_PATH), parent_lib))
+        L.pha_decode_attn.restype, L.pha_decode_attn.argtypes = _abi.SIGNATURES["pha_decode_attn"]
+        parent, tree = raw(L), raw(_lib.loaded())
+
+    print(f"### (c) per-row time steps: B={B} H={H} D={D} max_seq={MAX_SEQ} bf16, graph replay over {LAYERS} caches, "
+          f"us per call, median of {rounds} rounds x {reps} replays (min - max)\n")
+    print("| ts | scalar device step | per-row, equal steps | per-row - scalar |" +
+          (" scalar, direct call | parent scalar, direct call | this tree - parent |" if parent else "") + " outputs |")
+    print("|---|---|---|---|" + ("---|---|---|" if parent else "") + "---|")
+    for ts in (127, 1023, 2047):
+        one = torch.tensor([ts], dtype=torch.int32, device="cuda")
+        rows = torch.full((B,), ts, dtype=torch.int32, device="cuda")
+        c = [caches[0].clone() for _ in range(3)]
+        outs = [hip.decode_attention(qkv, qb, c[0], one), hip.decode_attention(qkv, qb, c[1], rows)]
+        if parent:
+            outs.append(parent(c[2], one).clone())
+        same = all(torch.equal(outs[0].view(torch.int16), o.view(torch.int16)) for o in outs[1:]) and all(
+            torch.equal(c[0].view(torch.int16), x.view(torch.int16)) for x in c[1:len(outs)])
+        fns = [lambda i: hip.decode_attention(qkv, qb, caches[i % LAYERS], one),
+               lambda i: hip.decode_attention(qkv, qb, caches[i % LAYERS], rows)]
+        if parent:
+            fns += [lambda i: tree(caches[i % LAYERS], one), lambda i: parent(caches[i % LAYERS], one)]
+        graphs = [capture(fn) for fn in fns]
+        res = alternate([lambda _, gr=gr: gr.replay() for gr in graphs], reps, rounds)
+        print(f"| {ts} | {us(res[0])} | {us(res[1])} | {within(res[1], res[0])} |" +
+              (f" {us(res[2])} | {us(res[3])} | {within(res[2], res[3])} |" if parent else "") +
+              f" {'bitwise equal' if same else 'DIFFER'} |")
+        del graphs
+    print()
+
+    spread = [round(128 + j * (2047 - 128) / (B - 1)) for j in range(B)]
+    arms = [("all at 2047", [2047] * B), ("spread evenly over 128..2047", spread)]
+    graphs, live = [], []
+    for _, steps in arms:
+        t = torch.tensor(steps, dtype=torch.int32, device="cuda")
+        graphs.append(capture(lambda i, t=t: hip.decode_attention(qkv, qb, caches[i % LAYERS], t)))
+        live.append(sum(x + 1 for x in steps))
+    res = alternate([lambda _, gr=gr: gr.replay() for gr in graphs], reps, rounds)
+    print(f"### (c) ragged steps, same shapes: steps {spread}\n")
+    print("| steps | live keys (sum over rows) | us per call | time / all-2047 | keys / all-2047 |")
+    print("|---|---|---|---|---|")
+    for (label, _), r, n in zip(arms, res, live):
+        print(f"| {label} | {n} | {us(r)} | {r[0] / res[0][0]:.2f} | {n / live[0]:.2f} |")
+    print()
+
+
 def bench_model(rounds, iters):
     E, DFF, ts = H * D, 4 * H * D, 1023
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -158,12 +255,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=960)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--skip-attention", action="store_true")
+    ap.add_argument("--rows", action="store_true", help="part (c): per-row time steps")
+    ap.add_argument("--parent-lib", default=None,
+                    help="file name under paddle_hackathon_amd/_C/ of a library built from the parent commit's "
+                         "decode_attn.hip, for the scalar arm of part (c)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode_attn needs a GPU")
     print(f"device: {torch.cuda.get_device_name(0)}, DECODE_ATTN_CHUNK = {hip.DECODE_ATTN_CHUNK}\n")
     with torch.no_grad():
-        bench_attention(a.rounds, a.iters)
+        if not a.skip_attention:
+            bench_attention(a.rounds, a.iters)
+        if a.rows:
+            bench_rows(a.rounds, a.iters, a.parent_lib)
     if not a.skip_model:
         bench_model(a.rounds, max(8, a.iters // LAYERS))
 

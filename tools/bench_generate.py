@@ -9,11 +9,14 @@
     search and once sampling with top-k 50 + top-p 0.9: replayed from the captured graph and eager, each
     with PHA_SAMPLE_KERNEL=0 and 1; tokens/s and ms per token over the whole call (prefill included).
 
+(d) with --ragged: the same model, B = 8, 128 new tokens, greedy, replayed from the graph: prompts of
+    16..128 tokens (``seq_lens``, a time step per row) against all eight at 128.
+
 The arms alternate in one process; medians over the rounds with min - max. "stays" is the rule of
 profiles/decode_gemm/README.md: the kernel's median is below the other arm's by more than the larger
 min - max spread of the two.
 
-Prints markdown tables. Usage: python tools/bench_generate.py [--rounds 7] [--iters 20] [--skip-model]
+Prints markdown tables. Usage: python tools/bench_generate.py [--rounds 7] [--iters 20] [--skip-model] [--ragged]
 """
 import argparse
 import os
@@ -156,6 +159,42 @@ def _generate_arms(gens, ids, new, rounds, what, kw, B, prompt):
     print(f"\nthe four arms return {'the same' if same else 'different'} tokens\n")
 
 
+def bench_ragged(rounds, B=8, prompt=128, new=128):
+    import paddle_hackathon_amd as paddle
+    from paddle_hackathon_amd.models import GPTForPretraining, GPTGenerator, gpt_config
+    paddle.set_device("gpu:0")
+    paddle.seed(0)
+    model = paddle.amp.decorate(GPTForPretraining(gpt_config("gpt3-1.3b")), level="O2", dtype="bfloat16")
+    model.eval()
+    ids = torch.randint(0, V, (B, prompt), device="cuda", generator=torch.Generator(device="cuda").manual_seed(2))
+    lens = [round(16 + j * (prompt - 16) / (B - 1)) for j in range(B)]
+    gen = GPTGenerator(model)
+    arms = [(f"all prompts {prompt} (one time step)", dict()), (f"prompts {lens} (seq_lens, a step per row)",
+                                                              dict(seq_lens=lens))]
+
+    def run(kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        gen.generate(ids, new, use_graph=True, **kw)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for _, kw in arms:
+        run(kw)   # warm-up: captures the graph
+    samples = [[] for _ in arms]
+    for _ in range(rounds):
+        for s, (_, kw) in zip(samples, arms):
+            s.append(run(kw))
+    print(f"### (d) generate, GPT-3 1.3B bf16, B = {B}, {new} new tokens, greedy, graph, whole call (prefill over "
+          f"{prompt} positions included), median of {rounds} rounds (min - max); {gen.captures} captures\n")
+    print("| prompts | ms per call | ms per token |")
+    print("|---|---|---|")
+    for (label, _), s in zip(arms, samples):
+        med, lo, hi = statistics.median(s), min(s), max(s)
+        print(f"| {label} | {med:.1f} ({lo:.1f} - {hi:.1f}) | {med / new:.3f} |")
+    print()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -163,6 +202,7 @@ def main():
     ap.add_argument("--skip-sampling", action="store_true")
     ap.add_argument("--skip-lm-head", action="store_true")
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--ragged", action="store_true", help="part (d): prompts of different lengths")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate needs a GPU")
@@ -174,6 +214,8 @@ def main():
             bench_lm_head(a.rounds, a.iters)
         if not a.skip_model:
             bench_generate(a.rounds)
+        if a.ragged:
+            bench_ragged(a.rounds)
 
 
 if __name__ == "__main__":
