@@ -29,6 +29,19 @@
 // range-checks it on its own (a bad row touches nothing and gets NaN, the others are unaffected)
 // and depends on no other row. ROWS is a template parameter: the scalar instantiation is the code
 // it was before.
+//
+// Beam-indirect form (pha_decode_attn_beam), for beam search: the B rows are groups of `beam`
+// consecutive beams, and a beam's history lies scattered over its group's cache rows. `ind` int32
+// [B, max_seq] names, per row and key position t < ts, the beam of the group whose cache row holds
+// that key: cache row (b / beam) * beam + ind[b, t]. Nothing is moved between cache rows. Position ts
+// is formed from the QKV product as above, appended to row b's own cache row and used from registers;
+// ind[b, ts] is never read. An entry outside [0, beam) is checked before any address is formed from it
+// and its key is left out as if masked. The rows of a group must share one step: a row reads its
+// siblings' cache rows below its own ts while they append at theirs. Each workgroup stages its
+// chunk's 128 table entries in LDS once (one coalesced 512-byte load and one barrier per workgroup,
+// instead of a dependent 4-byte load in front of every key's 16-byte loads). BEAM is one more
+// template parameter of the partial kernel; the scalar and per-row instantiations are the code they
+// were before.
 #include "common.h"
 
 namespace pha {
@@ -51,12 +64,22 @@ __device__ __forceinline__ void osm_merge(float& m, float& l, float (&o)[8], flo
   m = mn;
 }
 
+// the beam form's staged table entries; only that form instantiates it
+__device__ __forceinline__ int* beam_rows() {
+  __shared__ int rows[DECODE_ATTN_CHUNK];
+  return rows;
+}
+
 // ws: [B, H, nsplit, D + 2] fp32 rows of (o[D], m, l)
-template <typename T, int D, bool ROWS>
+// BEAM (with ROWS): key position t < ts of row b is read from cache row (b / beam) * beam + ind[b, t].
+// Everything that names `ind`, `beam`, `srow` or `in` stands in an `if constexpr (BEAM)`: the scalar
+// and per-row instantiations pass null and 1 and compile to the instructions they had before.
+template <typename T, int D, bool ROWS, bool BEAM>
 __global__ __launch_bounds__(DECODE_ATTN_THREADS) void decode_attn_partial(
     const T* __restrict__ qkv, const T* __restrict__ qkv_bias, T* __restrict__ cache,
     const float* __restrict__ mask, long mask_sb, long mask_sh, float scale, int ts_host,
-    const int* __restrict__ ts_dev, float* __restrict__ ws, int B, int H, int max_seq, int nsplit) {
+    const int* __restrict__ ts_dev, float* __restrict__ ws, int B, int H, int max_seq, int nsplit,
+    const int* __restrict__ ind, int beam) {
   constexpr int LPK = D / 8;                       // lanes per key
   constexpr int GPW = 64 / LPK;                    // lane groups per wave
   constexpr int G = DECODE_ATTN_WAVES * GPW;       // lane groups per workgroup
@@ -120,6 +143,22 @@ __global__ __launch_bounds__(DECODE_ATTN_THREADS) void decode_attn_partial(
 
   const float* mrow = mask ? mask + (size_t)b * mask_sb + (size_t)h * mask_sh : nullptr;
 
+  // BEAM: the chunk's table entries are staged once, already turned into the cache row to read
+  // (-1: the entry is outside [0, beam) and its key is left out). Entries at or above ts are not read.
+  [[maybe_unused]] int* srow = nullptr;
+  if constexpr (BEAM) {
+    srow = beam_rows();
+    if (tid < DECODE_ATTN_CHUNK) {
+      int r = -1;
+      if (k0 + tid < ts) {
+        const int e = ind[(size_t)b * max_seq + k0 + tid];
+        if (e >= 0 && e < beam) r = (b / beam) * beam + e;
+      }
+      srow[tid] = r;
+    }
+    __syncthreads();
+  }
+
   float m = -INFINITY, l = 0.f, o[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) o[j] = 0.f;
@@ -130,15 +169,27 @@ __global__ __launch_bounds__(DECODE_ATTN_THREADS) void decode_attn_partial(
     uint4 kr[U], vr[U];
     float mb[U];
     int key[U];
+    [[maybe_unused]] bool in[U];                   // BEAM: false where the table entry is out of range
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       key[u] = it + u * G + grp;
       kr[u] = vr[u] = make_uint4(0, 0, 0, 0);
       mb[u] = 0.f;
+      if constexpr (BEAM) in[u] = true;
       if (key[u] < kend) {
         if (key[u] != ts) {                        // position ts comes from registers, never from the cache
-          raw_ld8(kbase + (size_t)key[u] * D, kr[u]);
-          raw_ld8(kbase + vofs + (size_t)key[u] * D, vr[u]);
+          if constexpr (BEAM) {
+            const int src = srow[key[u] - k0];
+            in[u] = src >= 0;
+            if (in[u]) {
+              const T* kb = cache + (((size_t)src * H + h) * max_seq + key[u]) * D + sub * 8;
+              raw_ld8(kb, kr[u]);
+              raw_ld8(kb + vofs, vr[u]);
+            }
+          } else {
+            raw_ld8(kbase + (size_t)key[u] * D, kr[u]);
+            raw_ld8(kbase + vofs + (size_t)key[u] * D, vr[u]);
+          }
         }
         if (mrow) mb[u] = mrow[key[u]];
       }
@@ -159,6 +210,9 @@ __global__ __launch_bounds__(DECODE_ATTN_THREADS) void decode_attn_partial(
 #pragma unroll
       for (int off = 1; off < LPK; off <<= 1) d += __shfl_xor(d, off, 64);
       sc[u] = key[u] < kend ? d + mb[u] : -INFINITY;
+      if constexpr (BEAM) {
+        if (!in[u]) sc[u] = -INFINITY;
+      }
       mn = fmaxf(mn, sc[u]);
     }
     const float a = (m == -INFINITY) ? 0.f : __expf(m - mn);
@@ -246,13 +300,32 @@ static int decode_attn_launch(const void* qkv, const void* bias, void* cache, co
   const int nsplit = (max_seq + DECODE_ATTN_CHUNK - 1) / DECODE_ATTN_CHUNK;
   const dim3 grid(nsplit, H, B);
 #define PHA_DA_LAUNCH(DD)                                                                                \
-  decode_attn_partial<T, DD, ROWS><<<grid, DECODE_ATTN_THREADS, 0, st>>>(                                \
-      (const T*)qkv, (const T*)bias, (T*)cache, mask, msb, msh, scale, ts, ts_dev, ws, B, H, max_seq, nsplit)
+  decode_attn_partial<T, DD, ROWS, false><<<grid, DECODE_ATTN_THREADS, 0, st>>>(                         \
+      (const T*)qkv, (const T*)bias, (T*)cache, mask, msb, msh, scale, ts, ts_dev, ws, B, H, max_seq, nsplit, \
+      nullptr, 1)
   if (D == 32) PHA_DA_LAUNCH(32);
   else if (D == 64) PHA_DA_LAUNCH(64);
   else PHA_DA_LAUNCH(128);
 #undef PHA_DA_LAUNCH
   decode_attn_combine<T, ROWS><<<dim3(H, B), D, 0, st>>>(ws, (T*)out, ts, ts_dev, H, D, max_seq, nsplit);
+  return (int)hipGetLastError();
+}
+
+template <typename T>
+static int decode_attn_beam_launch(const void* qkv, const void* bias, void* cache, const float* mask, long msb, long msh,
+                                   float scale, const int* ts_rows, const int* ind, int beam, void* out, float* ws,
+                                   int B, int H, int D, int max_seq, hipStream_t st) {
+  const int nsplit = (max_seq + DECODE_ATTN_CHUNK - 1) / DECODE_ATTN_CHUNK;
+  const dim3 grid(nsplit, H, B);
+#define PHA_DA_LAUNCH(DD)                                                                                \
+  decode_attn_partial<T, DD, true, true><<<grid, DECODE_ATTN_THREADS, 0, st>>>(                          \
+      (const T*)qkv, (const T*)bias, (T*)cache, mask, msb, msh, scale, 0, ts_rows, ws, B, H, max_seq, nsplit, \
+      ind, beam)
+  if (D == 32) PHA_DA_LAUNCH(32);
+  else if (D == 64) PHA_DA_LAUNCH(64);
+  else PHA_DA_LAUNCH(128);
+#undef PHA_DA_LAUNCH
+  decode_attn_combine<T, true><<<dim3(H, B), D, 0, st>>>(ws, (T*)out, 0, ts_rows, H, D, max_seq, nsplit);
   return (int)hipGetLastError();
 }
 
@@ -291,5 +364,23 @@ PHA_API int pha_decode_attn_rows(int dt, const void* qkv, const void* qkv_bias, 
   if (dt == pha::kF16)
     return pha::decode_attn_launch<pha::half_t, true>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0, ts_rows,
                                                       out, ws, B, H, D, max_seq, stream);
+  return (int)hipErrorInvalidValue;
+}
+
+// The beam-indirect form: as pha_decode_attn_rows, with `ind` a device int32 table [B, max_seq] and
+// `beam` (it divides B) the number of rows in a group. Row b reads key position t < ts_rows[b] from
+// cache row (b / beam) * beam + ind[b, t] and appends position ts_rows[b] to its own cache row.
+PHA_API int pha_decode_attn_beam(int dt, const void* qkv, const void* qkv_bias, void* cache, const float* mask,
+                                 long mask_sb, long mask_sh, float scale, const int* ts_rows, const int* ind, int beam,
+                                 void* out, float* ws, int B, int H, int D, int max_seq, hipStream_t stream) {
+  if (B <= 0 || H <= 0 || max_seq <= 0 || B > 65535 || H > 65535 || (D != 32 && D != 64 && D != 128) || !ts_rows || !ind)
+    return (int)hipErrorInvalidValue;
+  if (beam < 1 || B % beam != 0) return (int)hipErrorInvalidValue;
+  if (dt == pha::kBF16)
+    return pha::decode_attn_beam_launch<pha::bf16_t>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts_rows, ind,
+                                                     beam, out, ws, B, H, D, max_seq, stream);
+  if (dt == pha::kF16)
+    return pha::decode_attn_beam_launch<pha::half_t>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts_rows, ind,
+                                                     beam, out, ws, B, H, D, max_seq, stream);
   return (int)hipErrorInvalidValue;
 }

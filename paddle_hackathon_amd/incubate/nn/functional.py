@@ -221,7 +221,7 @@ def fused_multi_head_attention(x, qkv_weight, linear_weight, pre_layer_norm=Fals
     return _wrap(o)
 
 
-def _decode_kernel_ok(qkv, cache, mask, device_time_step, dropout_rate, training):
+def _decode_kernel_ok(qkv, cache, mask, device_time_step, dropout_rate, training, cache_indirection=None, beam_size=1):
     """whether one decode step's attention (qkv [B, 3, H, D], the layer's cache) runs on the split-KV
     decode kernels (ops/hip.decode_attention). PHA_DECODE_ATTN=0 keeps the composite; on the GPU
     every other reason to keep it is recorded as a fallback."""
@@ -231,7 +231,7 @@ def _decode_kernel_ok(qkv, cache, mask, device_time_step, dropout_rate, training
         reason = "attention dropout"
     elif torch.is_grad_enabled() and qkv.requires_grad:
         reason = "needs a gradient (the decode kernels have no backward; run generation under no_grad)"
-    elif not _ops.hip.decode_attn_supported(qkv, cache, mask, device_time_step):
+    elif not _ops.hip.decode_attn_supported(qkv, cache, mask, device_time_step, cache_indirection, beam_size):
         reason = (f"{qkv.dtype} D={qkv.shape[-1]} cache {cache.dtype} {tuple(cache.shape)} "
                   f"mask={None if mask is None else tuple(mask.shape)}")
     else:
@@ -274,11 +274,47 @@ def _decode_rows_composite(q, k, v, c, ts_rows, mask, dropout_rate, training, mo
     return _attention(q, kk, vv, m.to(q.dtype), dropout_rate, training, mode, causal=False)
 
 
+def _decode_beam_composite(q, k, v, c, ts_rows, ind, beam, mask, dropout_rate, training, mode):
+    """the decode stage's attention through a cache-indirection table, on the composite: as
+    _decode_rows_composite, with row b's key position t < ts_rows[b] taken from cache row
+    ``(b // beam) * beam + ind[b, t]``. The new key and value are appended to row b's own cache row;
+    each row's history is gathered through the table into a temporary [2, B, H, max_seq, D] and
+    _decode_rows_composite's arithmetic runs on that. A table entry outside [0, beam) leaves its key
+    out (zeroed and masked); the entry at ts_rows[b] is not read. No host sync on the GPU."""
+    B, max_seq = c.shape[1], c.shape[3]
+    idx = ts_rows.reshape(-1).long()
+    ok = ((idx >= 0) & (idx < max_seq))[:, None, None]
+    at = idx.clamp(0, max_seq - 1)
+    rows = torch.arange(B, device=c.device)
+    c[0][rows, :, at] = torch.where(ok, k[:, :, 0], c[0][rows, :, at])
+    c[1][rows, :, at] = torch.where(ok, v[:, :, 0], c[1][rows, :, at])
+    t = torch.arange(max_seq, device=c.device)
+    below = t[None, :] < idx[:, None]                                                  # [B, max_seq]
+    valid = (ind >= 0) & (ind < beam) | ~below
+    src = torch.where(below, (rows // beam * beam)[:, None] + ind.long().clamp(0, beam - 1), rows[:, None])
+    zero = torch.zeros((), dtype=c.dtype, device=c.device)
+    # the two index tensors are split by a slice, so their [B, max_seq] comes first: [B, max_seq, 2, H, D]
+    tmp = torch.where(valid[:, :, None, None, None], c[:, src, :, t[None, :]], zero).permute(2, 0, 3, 1, 4).contiguous()
+    extra = torch.zeros(B, 1, 1, max_seq, dtype=torch.float32, device=c.device).masked_fill_(
+        ~valid[:, None, None, :], float("-inf"))
+    if mask is not None:
+        um = mask
+        if um.dtype == torch.bool:
+            um = torch.zeros(um.shape, dtype=torch.float32, device=um.device).masked_fill_(~um, float("-inf"))
+        um = um.to(device=c.device, dtype=torch.float32)
+        while um.dim() < 4:
+            um = um.unsqueeze(0)
+        if um.shape[-1] != 1 and um.shape[-1] < max_seq:
+            extra = extra[..., :um.shape[-1]]
+        extra = extra + um
+    return _decode_rows_composite(q, k, v, tmp, ts_rows, extra, dropout_rate, training, mode)
+
+
 def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, linear_weights, linear_biases,
                             ffn_ln_scales, ffn_ln_biases, ffn1_weights, ffn1_biases, ffn2_weights, ffn2_biases,
                             pre_layer_norm=True, epsilon=1e-05, cache_kvs=None, time_step=None, attn_mask=None,
                             dropout_rate=0.0, activation="gelu", training=False, mode="upscale_in_train",
-                            trans_qkvw=True, ring_id=-1, name=None):
+                            trans_qkvw=True, ring_id=-1, name=None, cache_indirection=None, beam_size=1):
     """Stack of pre-LN decoder layers for generation. ``cache_kvs[i]`` is a preallocated
     [2, B, H, max_seq, D] buffer updated in place: context stage (time_step None) writes
     positions [0, S); decode stage (S == 1) writes position ``time_step`` and attends over
@@ -295,7 +331,16 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     either ``trans_qkvw`` layout without a transposed copy, the output projection and ffn2 with bias
     and residual add in the epilogue (where dropout is an identity and ``ring_id < 0``), ffn1 with bias + GELU / ReLU.
     ``activation`` is "gelu" (erf), "gelu_tanh" (the tanh approximation the GPT model trains with) or "relu".
-    PHA_DECODE_GEMM=0 keeps the library GEMMs and the separate elementwise passes."""
+    PHA_DECODE_GEMM=0 keeps the library GEMMs and the separate elementwise passes.
+
+    ``cache_indirection`` (contiguous int32 [B, max_seq] on the device of ``x``) with ``beam_size`` K
+    (it divides B) serves beam search and applies to the decode stage only (anything else is a
+    ``ValueError``): the B rows are groups of K consecutive beams that share one step, and row b reads
+    key position t < time_step from cache row ``(b // K) * K + cache_indirection[b, t]`` of every
+    layer's cache, while the new key and value go to row b's own cache row. The kernel pair takes the
+    table as it is (``ops.hip.decode_attention``); the composite gathers each row's keys and values
+    through it into a temporary, without a host sync on the GPU. A scalar ``time_step`` is broadcast
+    to the B rows."""
     h = _u(x)
     B, S, E = h.shape
     ts = ts_dev = ts_rows = None
@@ -315,6 +360,23 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             ts = int(t.reshape(-1)[0].item()) if isinstance(t, torch.Tensor) else int(t)
     mask = _u(attn_mask)
     decode = cache_kvs is not None and time_step is not None and S == 1
+    ind = _u(cache_indirection)
+    if ind is None:
+        if beam_size != 1:
+            raise ValueError(f"fused_multi_transformer: beam_size={beam_size!r} needs a cache_indirection table")
+    else:
+        if not decode:
+            raise ValueError("fused_multi_transformer: cache_indirection applies to the decode stage only "
+                             "(cache_kvs, a time_step and one new token per row)")
+        why = _ops.hip._cache_indirection_why_not(ind, beam_size, B, _u(cache_kvs[0]).shape[3], h.device)
+        if why is not None:
+            raise ValueError(f"fused_multi_transformer: {why}")
+        if ts_rows is None:   # the table's paths take a step per row
+            ts_rows = ts_dev.reshape(1).expand(B).contiguous() if ts_dev is not None \
+                else torch.full((B,), ts, dtype=torch.int32, device=h.device)
+            ts = None
+            if h.is_cuda:
+                ts_dev = ts_rows
     # at most 16 rows: the products may run on the weight-streaming kernels (_skinny_ok decides each)
     skinny = isinstance(h, torch.Tensor) and h.is_cuda and B * S <= _ops.hip.SKINNY_GEMM_MAX_M
     # bias and residual add go into the epilogue only where nothing stands between them and the product
@@ -339,7 +401,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             # goes into this product's epilogue
             use_decode = decode and _decode_kernel_ok(a2.as_strided((B, 3, H, D), (0, 0, 0, 0)), _u(cache_kvs[i]), mask,
                                                       ts_dev if ts_dev is not None else False, dropout_rate,
-                                                      training)
+                                                      training, ind, beam_size)
             qbe = None if use_decode or qb is None else qb.reshape(-1)
             if qbe is not None and not _ops.hip.skinny_gemm_supported(a2, w2, trans_qkvw, qbe):
                 qbe = None   # added below as today
@@ -349,13 +411,19 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         else:
             qkv = a2 @ (w2.t() if trans_qkvw else w2)
             use_decode = decode and _decode_kernel_ok(qkv.reshape(B, 3, H, D), _u(cache_kvs[i]), mask,
-                                                      ts_dev if ts_dev is not None else False, dropout_rate, training)
+                                                      ts_dev if ts_dev is not None else False, dropout_rate, training,
+                                                      ind, beam_size)
         if use_decode:
             # one split-KV kernel pair: bias add, cache append and attention over [0, time_step]
             if qb is not None and (qb.dtype != qkv.dtype or not qb.is_contiguous()):
                 qb = qb.to(qkv.dtype).contiguous()
-            o = _ops.hip.decode_attention(qkv.reshape(B, 3, H, D), None if qb is None else qb.reshape(3, H, D),
-                                          _u(cache_kvs[i]), ts_dev if ts_dev is not None else ts, mask)
+            if ind is not None:
+                o = _ops.hip.decode_attention(qkv.reshape(B, 3, H, D), None if qb is None else qb.reshape(3, H, D),
+                                              _u(cache_kvs[i]), ts_dev, mask, cache_indirection=ind,
+                                              beam_size=beam_size)
+            else:
+                o = _ops.hip.decode_attention(qkv.reshape(B, 3, H, D), None if qb is None else qb.reshape(3, H, D),
+                                              _u(cache_kvs[i]), ts_dev if ts_dev is not None else ts, mask)
         else:
             if ts_dev is not None and ts is None and ts_rows is None:
                 ts = int(ts_dev.item())
@@ -364,7 +432,10 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             qkv = qkv.reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
             q, k, v = qkv[0], qkv[1], qkv[2]
             causal = False
-            if ts_rows is not None:
+            if ind is not None:
+                o = _decode_beam_composite(q, k, v, _u(cache_kvs[i]), ts_rows, ind, beam_size, mask, dropout_rate,
+                                           training, mode)
+            elif ts_rows is not None:
                 o = _decode_rows_composite(q, k, v, _u(cache_kvs[i]), ts_rows, mask, dropout_rate, training, mode)
             elif cache_kvs is not None:
                 c = _u(cache_kvs[i])

@@ -270,9 +270,10 @@ class GPTForPretraining(nn.Layer):
         return _wrap(_cg.matmul_nt(h._t, w._t))
 
     def generate(self, input_ids, max_new_tokens, **kwargs):
-        """cached generation (greedy search or temperature / top-k / top-p sampling) with a KV cache:
-        ``models.gpt_generate.GPTGenerator.generate`` on a generator kept with the model. Prompts of
-        different lengths go in as one padded batch with ``seq_lens`` or ``attention_mask``."""
+        """cached generation (greedy search, temperature / top-k / top-p sampling, or beam search with
+        ``decode_strategy="beam_search"``, ``num_beams``, ``num_return_sequences`` and ``length_penalty``)
+        with a KV cache: ``models.gpt_generate.GPTGenerator.generate`` on a generator kept with the model.
+        Prompts of different lengths go in as one padded batch with ``seq_lens`` or ``attention_mask``."""
         gen = self.__dict__.get("_generator")
         if gen is None:
             from .gpt_generate import GPTGenerator

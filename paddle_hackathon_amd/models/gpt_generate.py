@@ -19,6 +19,13 @@ b takes its first token from position ``len_b - 1`` and then decodes with a time
 ``time_step`` being int32 ``[B]``. It overwrites the stale padding rows of its cache as it goes and
 never reads a key above its step, so a step streams the live keys of every row and no padding.
 
+Beam search (``decode_strategy="beam_search"``) runs R = B * num_beams rows, row b * K + k being beam k
+of item b, through the same step with ``ops.hip.beam_search_step`` in place of the sampler. A beam's
+keys stay where they were written: every layer's attention reads them through one int32
+``cache_indirection`` table [R, cache length] that the beam step re-orders in place, so nothing is
+copied between cache rows, and the prompt is computed and stored once per item (in beam 0's cache row,
+which the table names everywhere at the start).
+
 The model's own parameters are used: ``nn.Linear`` weights are ``[in, out]``, the ``[K, N]`` layout
 of the kernels, and go in as views. The one exception is the fused QKV projection, whose outputs are
 ordered (head, 3, D) while the decode kernels need (3, head, D): the generator keeps one repacked
@@ -36,7 +43,7 @@ from ..framework.core import Tensor, _wrap
 from .. import ops as _ops
 from ..ops import conv_gemm as _cg
 
-STRATEGIES = ("greedy_search", "sampling")
+STRATEGIES = ("greedy_search", "sampling", "beam_search")
 EOS_CHECK_EVERY = 16   # decode steps between two host reads of finished.all()
 
 
@@ -55,13 +62,34 @@ class _GraphState:
         self.weights_at = None
 
 
+class _BeamState:
+    """the static buffers of one captured beam-search step (R = B * K rows), and the graph once it exists"""
+
+    def __init__(self, B, K, cache_len, cfg, dtype, device):
+        H, D, R = cfg.num_heads, cfg.head_dim, B * K
+        self.caches = [torch.zeros(2, R, H, cache_len, D, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
+        self.tok = torch.zeros(R, dtype=torch.int64, device=device)
+        self.ts = torch.zeros(R, dtype=torch.int32, device=device)        # always a step per row
+        self.cum = torch.zeros(R, dtype=torch.float32, device=device)
+        self.finished = torch.zeros(R, dtype=torch.uint8, device=device)
+        self.lens = torch.zeros(R, dtype=torch.int32, device=device)
+        self.ind = torch.zeros(R, cache_len, dtype=torch.int32, device=device)   # the cache-indirection table
+        self.out = None
+        self.graph = None
+        self.weights_at = None
+
+    def state(self):
+        return (self.tok, self.ts, self.cum, self.finished, self.lens, self.ind)
+
+
 class GPTGenerator:
     """Cached generation over a ``GPTForPretraining`` (see the module docstring)."""
 
     def __init__(self, model):
         self.model = model
         self._qkv = {}        # layer index -> (weight version, bias version, repacked weight, repacked bias)
-        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged) -> _GraphState
+        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged) -> _GraphState;
+        #                       (B, cache length, "beam_search", num_beams, eos) -> _BeamState
         self._eager = set()   # keys whose warm-up step left the kernel path: not tried again
         self.captures = 0     # hipGraph captures so far (a second generate call adds none)
         self.last_caches = None
@@ -105,11 +133,11 @@ class GPTGenerator:
             w["f2_b"].append(layer.mlp.linear2.bias._t)
         return [w[k] for k in names]
 
-    def _stack(self, x, weights, caches, time_step=None):
+    def _stack(self, x, weights, caches, time_step=None, **beam):
         from ..incubate.nn import functional as FF
         out, _ = FF.fused_multi_transformer(x, *weights, pre_layer_norm=True, epsilon=self.model.cfg.layer_norm_eps,
                                             cache_kvs=caches, time_step=time_step, activation="gelu_tanh",
-                                            trans_qkvw=False)
+                                            trans_qkvw=False, **beam)
         return out._t
 
     def _logits(self, h):
@@ -139,6 +167,19 @@ class GPTGenerator:
         st.tok.copy_(ids)
         st.ts.add_(1)
         return ids, lp
+
+    def _beam_step(self, weights, st, s):
+        """one beam-search token: reads st.tok / st.ts and the beam state, appends to st.caches through
+        st.ind, replaces the beam state and st.tok, advances st.ts; returns (token, parent, logprob)"""
+        emb = self.model.gpt.embeddings
+        x = _ops.fused.embedding(st.tok, emb.word_embeddings.weight._t) \
+            + emb.position_embeddings.weight._t.index_select(0, st.ts)
+        h = self._stack(x.unsqueeze(1), weights, st.caches, st.ts, cache_indirection=st.ind, beam_size=s["beams"])
+        out = _ops.hip.beam_search_step(self._logits(h.reshape(h.shape[0], -1)), st.cum, st.finished, st.lens,
+                                        s["eos"], s["beams"], st.ind, st.ts)
+        st.tok.copy_(out[0])
+        st.ts.add_(1)
+        return out
 
     # ------------------------------------------------------------------------------ prompts
     @staticmethod
@@ -184,7 +225,8 @@ class GPTGenerator:
     # ------------------------------------------------------------------------------ generate
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, decode_strategy="greedy_search", temperature=1.0, top_k=0, top_p=1.0,
-                 eos_token_id=None, pad_token_id=0, seed=None, use_graph=None, seq_lens=None, attention_mask=None):
+                 eos_token_id=None, pad_token_id=0, seed=None, use_graph=None, seq_lens=None, attention_mask=None,
+                 num_beams=None, num_return_sequences=1, length_penalty=0.0):
         """``max_new_tokens`` tokens after ``input_ids`` [B, prompt]: (ids int64 [B, max_new_tokens],
         scores fp32 [B, max_new_tokens]), the score being the log probability of the token under the
         temperature-scaled, unfiltered softmax (0 at padded positions).
@@ -207,6 +249,22 @@ class GPTGenerator:
         with a time step per row, reading no padding. Without either argument, or with all lengths
         equal, the call is the uniform one, bit for bit.
 
+        ``decode_strategy`` "beam_search" keeps the ``num_beams`` (K) best continuations of every prompt
+        by cumulative log probability (no temperature, ``top_k`` or ``top_p``: a non-default value is a
+        ``ValueError``, as is ``num_beams != 1`` with the other strategies). ``num_beams`` has no default
+        with beam search: the call runs B * num_beams rows per step, so the width is the caller's to
+        name, and leaving it out is a ``ValueError``. A beam that emits
+        ``eos_token_id`` is finished and keeps its score. At the end each item's beams are ranked by
+        ``score / length ** length_penalty`` (0.0: the plain score; a stable sort) and the first
+        ``num_return_sequences`` are returned: ids int64 [B * num_return_sequences, max_new_tokens], the
+        best beam first per item, ``pad_token_id`` after a beam's first EOS, and scores of the same
+        shape, the log probability of each token along the beam's own history (0 at padded
+        positions), so a row of scores sums to the beam's score. ``num_beams=1`` is greedy search, bit
+        for bit. The step runs R = B * K rows; up to 16 rows it stays on the kernels and is captured
+        like the other strategies (the graph is kept per (B, cache length, num_beams, eos)), above
+        that it runs eagerly on the composites and library GEMMs (recorded as fallbacks). The prompt
+        is prefilled once per item, not once per beam.
+
         The model must be in eval mode with ``tensor_parallel_degree == 1``, and
         ``longest prompt + max_new_tokens <= max_position_embeddings``.
 
@@ -224,6 +282,22 @@ class GPTGenerator:
             raise RuntimeError("generate: the model is in training mode; call model.eval() first")
         if decode_strategy not in STRATEGIES:
             raise ValueError(f"generate: decode_strategy must be one of {STRATEGIES}, got {decode_strategy!r}")
+        beam = decode_strategy == "beam_search"
+        if num_beams is None:
+            if beam:   # there is no default width: the cost of a call is B * num_beams rows per step
+                raise ValueError("generate: decode_strategy='beam_search' needs num_beams (the number of beams per "
+                                 "prompt; 1 is greedy search)")
+            num_beams = 1
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or num_beams < 1:
+            raise ValueError(f"generate: num_beams={num_beams!r} must be an int of at least 1")
+        if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) \
+                or not 1 <= num_return_sequences <= num_beams:
+            raise ValueError(f"generate: num_return_sequences={num_return_sequences!r} must be an int in "
+                             f"[1, num_beams={num_beams}]")
+        if not beam and num_beams != 1:
+            raise ValueError(f"generate: num_beams={num_beams} needs decode_strategy='beam_search'")
+        if beam and (float(temperature) != 1.0 or int(top_k) != 0 or float(top_p) != 1.0):
+            raise ValueError("generate: beam search takes no temperature, top_k or top_p")
         ids_in = input_ids._t if isinstance(input_ids, Tensor) else torch.as_tensor(input_ids)
         if ids_in.dim() != 2 or ids_in.shape[0] < 1 or ids_in.shape[1] < 1:
             raise ValueError(f"generate: input_ids must be [B, prompt], got {tuple(ids_in.shape)}")
@@ -245,6 +319,11 @@ class GPTGenerator:
         if use_graph and not wte.is_cuda:
             raise RuntimeError("generate: use_graph=True needs the model on a GPU")
         cache_len = P + n_new
+        if beam:
+            if num_beams > cfg.vocab_size:
+                raise ValueError(f"generate: num_beams={num_beams} exceeds the vocabulary ({cfg.vocab_size})")
+            s.update(beams=num_beams, nret=num_return_sequences, length_penalty=float(length_penalty))
+            return self._generate_beam(ids_in, lens, n_new, s, use_graph)
         key = (B, cache_len, s["strategy"], s["temperature"], s["top_k"], s["top_p"], s["eos"], s["pad"], ragged)
         weights = self._layer_weights()
         want_graph = wte.is_cuda and use_graph is not False and n_new > 1 \
@@ -342,5 +421,119 @@ class GPTGenerator:
             st.ids, st.logprob = self._step(weights, st, s)
         self.captures += 1
         self._set_ts(st, ts0)   # capture launches nothing: the first replay is step 0
+        st.graph, st.weights_at = g, at
+        return g
+
+    # ------------------------------------------------------------------------------ beam search
+    def _generate_beam(self, ids_in, lens, n_new, s, use_graph):
+        """generate()'s beam-search branch: ``ids_in`` [B, P] on the device, ``lens`` the prompt
+        lengths or None"""
+        model, cfg = self.model, self.model.cfg
+        wte = model.gpt.embeddings.word_embeddings.weight._t
+        dev, dtype = wte.device, wte.dtype
+        B, P = ids_in.shape
+        K, eos = s["beams"], s["eos"]
+        R, cache_len = B * K, P + n_new
+        key = (B, cache_len, "beam_search", K, eos)
+        weights = self._layer_weights()
+        want_graph = wte.is_cuda and use_graph is not False and n_new > 1 \
+            and (bool(use_graph) or key not in self._eager)
+        st = self._graphs.get(key) if want_graph else None
+        if st is None:
+            st = _BeamState(B, K, cache_len, cfg, dtype, dev)
+        else:
+            for c in st.caches:
+                c.zero_()
+            for t in (st.finished, st.lens, st.ind):
+                t.zero_()
+        self.last_caches = st.caches
+        # per group: beam 0 starts at 0, the others at -inf, so the first step's K picks all continue beam 0
+        st.cum.copy_(torch.tensor([0.0] + [float("-inf")] * (K - 1), dtype=torch.float32).repeat(B))
+
+        # prefill over the B prompts only, into beam 0's cache row of every group (a strided view)
+        x = model.gpt.embeddings(_wrap(ids_in))._t
+        h = self._stack(x, weights, [c[:, ::K] for c in st.caches])
+        if lens is not None and min(lens) != P:
+            ts0 = torch.tensor(lens, dtype=torch.int32).to(dev)
+            last = h[torch.arange(B, device=dev), ts0.long() - 1]
+            ts0 = ts0.repeat_interleave(K)
+        else:
+            ts0, last = torch.full((R,), P, dtype=torch.int32, device=dev), h[:, -1]
+        # the first token: the B logit rows K times through the same beam step, at the prompt's last position
+        logits = self._logits(last.contiguous()).repeat_interleave(K, 0)
+        toks = torch.zeros((n_new, R), dtype=torch.int64, device=dev)
+        pars = torch.zeros((n_new, R), dtype=torch.int64, device=dev)
+        lps = torch.zeros((n_new, R), dtype=torch.float32, device=dev)
+        st.ts.copy_(ts0 - 1)
+        tok, parent, lp = _ops.hip.beam_search_step(logits, st.cum, st.finished, st.lens, eos, K, st.ind, st.ts)
+        toks[0], pars[0], lps[0] = tok, parent, lp
+        st.tok.copy_(tok)
+        st.ts.copy_(ts0)
+
+        graph = None
+        if want_graph:
+            graph = self._beam_graph_for(st, weights, s, ts0, required=bool(use_graph))
+            if graph is not None:
+                self._graphs[key] = st
+            else:
+                self._eager.add(key)
+        self.last_steps, T = 0, 1
+        for j in range(1, n_new):
+            self.last_steps = j
+            if graph is not None:
+                graph.replay()
+                tok, parent, lp = st.out
+            else:
+                tok, parent, lp = self._beam_step(weights, st, s)
+            toks[j], pars[j], lps[j] = tok, parent, lp
+            T = j + 1
+            if eos >= 0 and j % EOS_CHECK_EVERY == 0 and bool(st.finished.all()):
+                break
+
+        # back-trace the K histories, rank each group, keep the first nret
+        from ..nn.functional.common import gather_tree
+        par3 = pars[:T].reshape(T, B, K)
+        seq = gather_tree(toks[:T].reshape(T, B, K), par3)._t           # [T, B, K]
+        slp = gather_tree(lps[:T].reshape(T, B, K), par3)._t
+        rank = st.cum.reshape(B, K)
+        if s["length_penalty"] != 0.0:
+            rank = rank / st.lens.reshape(B, K).clamp(min=1).float() ** s["length_penalty"]
+        order = torch.sort(rank, dim=-1, descending=True, stable=True).indices[:, :s["nret"]]   # [B, nret]
+        pick = order[None].expand(T, B, s["nret"])
+        seq = seq.gather(2, pick).permute(1, 2, 0).reshape(B * s["nret"], T)
+        slp = slp.gather(2, pick).permute(1, 2, 0).reshape(B * s["nret"], T)
+        is_eos = seq == eos
+        padded = (is_eos.cumsum(1) - is_eos.long()) > 0                   # after the beam's first EOS
+        out_ids = torch.full((B * s["nret"], n_new), s["pad"], dtype=torch.int64, device=dev)
+        out_lp = torch.zeros((B * s["nret"], n_new), dtype=torch.float32, device=dev)
+        out_ids[:, :T] = torch.where(padded, s["pad"], seq)
+        out_lp[:, :T] = torch.where(padded, 0.0, slp)
+        return _wrap(out_ids), _wrap(out_lp)
+
+    def _beam_graph_for(self, st, weights, s, ts0, required):
+        """_graph_for for the beam-search step: the warm-up step runs on a copy of the beam state"""
+        at = tuple(t.data_ptr() for group in weights for t in group)
+        if st.graph is not None and st.weights_at == at:
+            return st.graph
+        from ..ops import fallback
+        keep = [t.clone() for t in st.state()]
+        before = fallback.total()
+        self._beam_step(weights, st, s)   # warm-up: what it appends at the first step is rewritten by the first replay
+        clean = fallback.total() == before and os.environ.get("PHA_DECODE_ATTN", "1") != "0" \
+            and os.environ.get("PHA_BEAM_KERNEL", "1") != "0" \
+            and st.caches[0].dtype in (torch.bfloat16, torch.float16) and self.model.cfg.head_dim in (32, 64, 128)
+        for t, k in zip(st.state(), keep):
+            t.copy_(k)
+        if not clean and not required:
+            for c in st.caches:
+                c[:, torch.arange(c.shape[1], device=c.device), :, ts0.long()] = 0
+            return None
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            st.out = self._beam_step(weights, st, s)
+        self.captures += 1
+        for t, k in zip(st.state(), keep):   # capture launches nothing: the first replay is step 0
+            t.copy_(k)
         st.graph, st.weights_at = g, at
         return g

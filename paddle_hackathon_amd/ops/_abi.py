@@ -22,6 +22,10 @@ SIGNATURES = {
     "pha_bn_fwd_train": (I, [I, P, P, P, LG, I, P, P, P, P, P, P, P, P, P, F, F, I, P, I, P]),
     "pha_bn_apply": (I, [I, P, P, P, LG, I, P, P, I, P]),
     "pha_bn_bwd": (I, [I, P, P, P, LG, I, P, P, P, P, P, P, P, P, P, I, P, P, I, P]),
+    # beam_search.hip
+    "pha_beam_search_max_v": (I, []),
+    "pha_beam_search_max_k": (I, []),
+    "pha_beam_search_step": (I, [I, P, LG, P, P, P, P, P, P, P, P, P, P, I, I, I, LG, I, P]),
     # ce_gelu_embed.hip
     "pha_softmax_ce_fwd": (I, [I, P, P, P, P, LG, I, I, P]),
     "pha_softmax_ce_bwd": (I, [I, P, P, P, P, P, LG, I, I, P]),
@@ -41,6 +45,7 @@ SIGNATURES = {
     "pha_decode_attn_chunk": (I, []),
     "pha_decode_attn": (I, [I, P, P, P, P, LG, LG, F, I, P, P, P, I, I, I, I, P]),
     "pha_decode_attn_rows": (I, [I, P, P, P, P, LG, LG, F, P, P, P, I, I, I, I, P]),
+    "pha_decode_attn_beam": (I, [I, P, P, P, P, LG, LG, F, P, P, I, P, P, I, I, I, I, P]),
     # flash_attn.hip
     "pha_flash_attn_fwd_ext": (I, [I, P, P, P, P, P, I, I, I, I, I, I, F, I, P, LG, LG, LG, F, U, P, P]),
     "pha_flash_attn_bwd_ext": (I, [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P, LG, LG, LG, F, U, P, LG,

@@ -1090,13 +1090,27 @@ def _decode_attn_chunk():
 DECODE_ATTN_CHUNK = _decode_attn_chunk()   # key positions per split (0: library not built)
 
 
-def decode_attn_supported(qkv, cache, mask=None, device_time_step=False):
+def _cache_indirection_why_not(cache_indirection, beam_size, B, max_seq, device):
+    """why ``cache_indirection`` / ``beam_size`` do not fit B rows and a cache of max_seq positions on
+    ``device``, or None (the check decode_attention, decode_attn_supported and the composite share)"""
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or beam_size < 1 or B % beam_size:
+        return f"beam_size={beam_size!r} must be a positive int that divides the {B} rows"
+    t = cache_indirection
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B, max_seq) \
+            or t.device != device or not t.is_contiguous():
+        return f"cache_indirection must be a contiguous int32 [{B}, {max_seq}] tensor on {device}"
+    return None
+
+
+def decode_attn_supported(qkv, cache, mask=None, device_time_step=False, cache_indirection=None, beam_size=1):
     """what the decode kernel takes: a bf16 / fp16 [B, 3, H, D] QKV product with D in 32 / 64 / 128,
     a [2, B, H, max_seq, D] cache of the same dtype and device, and an optional additive / boolean
     mask broadcastable to [B, H, 1, keys] that needs no gradient (with a device time step its key
     dimension must span the whole cache, or be 1). ``device_time_step`` is a bool or the time-step
     tensor itself, which is then checked too: int32, on the device of ``qkv``, one element (one step
-    for the batch) or B elements (a step per batch row)"""
+    for the batch) or B elements (a step per batch row). With ``cache_indirection`` (contiguous int32
+    [B, max_seq] on the device of ``qkv``) ``beam_size`` must divide B; without it ``beam_size`` must
+    be 1"""
     if not DECODE_ATTN_CHUNK:
         return False
     if not (isinstance(qkv, torch.Tensor) and isinstance(cache, torch.Tensor) and qkv.is_cuda and cache.is_cuda):
@@ -1114,6 +1128,11 @@ def decode_attn_supported(qkv, cache, mask=None, device_time_step=False):
             return False
         device_time_step = True
     if tuple(cache.shape[:3]) != (2, B, H) or cache.shape[4] != D or cache.shape[3] < 1 or not cache.is_contiguous():
+        return False
+    if cache_indirection is None:
+        if beam_size != 1:
+            return False
+    elif _cache_indirection_why_not(cache_indirection, beam_size, B, cache.shape[3], qkv.device) is not None:
         return False
     if mask is not None:
         if not isinstance(mask, torch.Tensor) or mask.requires_grad or mask.dim() > 4 or mask.dim() < 1:
@@ -1148,7 +1167,7 @@ def _decode_bias(mask, B, H, need, device):
     return mask, (mask.stride(0), mask.stride(1))
 
 
-def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
+def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None, cache_indirection=None, beam_size=1):
     """One decode step of cached attention on the split-KV kernels. ``qkv`` [B, 3, H, D] is the raw
     QKV product of the new token and ``qkv_bias`` [3, H, D] (or None) its bias; the biased key and
     value are written to ``cache`` [2, B, H, max_seq, D] at ``time_step`` in place, and the biased,
@@ -1157,14 +1176,30 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
     left alone and the output is NaN): one element is the step of the whole batch, B elements give
     batch row b its own step ``time_step[b]`` (row b appends at it and reads no key above it; a row
     out of range is left alone and gets NaN, the others are unaffected). At B == 1 the two forms
-    coincide. Returns [B, 1, H * D]."""
+    coincide.
+
+    ``cache_indirection`` (contiguous int32 [B, max_seq] on the device, checked like ``time_step``)
+    with ``beam_size`` K (it divides B) is the beam-search form: the rows are groups of K consecutive
+    beams, and row b reads key position t < time_step from cache row ``(b // K) * K +
+    cache_indirection[b, t]``, so a beam follows its history through its group's cache rows and
+    nothing is copied between them. Position ``time_step`` is appended to row b's own cache row;
+    ``cache_indirection[b, time_step]`` is not read, and an entry outside [0, K) leaves its key out
+    as if masked. The rows of a group must share one step. One entry point serves it with a step
+    per row: a Python int or one-element ``time_step`` is broadcast to [B]. Returns [B, 1, H * D]."""
     fn = "decode_attention"
     if isinstance(time_step, torch.Tensor) and isinstance(qkv, torch.Tensor) and qkv.dim() == 4:
         if time_step.dtype != torch.int32 or time_step.device != qkv.device \
                 or time_step.numel() not in (1, qkv.shape[0]) or not time_step.is_contiguous():
             raise ValueError(f"{fn}: a tensor time_step must be contiguous int32 on {qkv.device} with one element "
                              f"or one per batch row ({qkv.shape[0]})")
-    if not decode_attn_supported(qkv, cache, mask, isinstance(time_step, torch.Tensor)):
+    if cache_indirection is None:
+        if beam_size != 1:
+            raise ValueError(f"{fn}: beam_size={beam_size!r} needs a cache_indirection table")
+    elif isinstance(qkv, torch.Tensor) and qkv.dim() == 4 and isinstance(cache, torch.Tensor) and cache.dim() == 5:
+        why = _cache_indirection_why_not(cache_indirection, beam_size, qkv.shape[0], cache.shape[3], qkv.device)
+        if why is not None:
+            raise ValueError(f"{fn}: {why}")
+    if not decode_attn_supported(qkv, cache, mask, isinstance(time_step, torch.Tensor), cache_indirection, beam_size):
         raise ValueError(f"{fn}: unsupported arguments (see decode_attn_supported)")
     B, _, H, D = qkv.shape
     max_seq = cache.shape[3]
@@ -1192,6 +1227,15 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None):
     ws = torch.empty((B, H, nsplit, D + 2), dtype=torch.float32, device=dev)
     out = torch.empty((B, 1, H * D), dtype=qkv.dtype, device=dev)
     sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(D))
+    if cache_indirection is not None:   # the beam-indirect form always takes a step per row
+        if ts_dev is None:
+            ts_dev = torch.full((B,), ts, dtype=torch.int32, device=dev)
+        elif ts_dev.numel() != B:
+            ts_dev = ts_dev.reshape(1).expand(B).contiguous()
+        _check(_L().pha_decode_attn_beam(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc,
+                                         _ptr(ts_dev), _ptr(cache_indirection), int(beam_size), _ptr(out), _ptr(ws),
+                                         B, H, D, max_seq, _stream(qkv)), fn)
+        return out
     if ts_dev is not None and ts_dev.numel() > 1:   # a step per batch row
         _check(_L().pha_decode_attn_rows(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc,
                                          _ptr(ts_dev), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
@@ -1499,3 +1543,196 @@ def sample_logits(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None,
     if out_logprob is not None:
         lp = out_logprob.copy_(lp)
     return ids, lp
+
+
+# ----------------------------------------------------------------------------
+# beam-search step (csrc/kernels/beam_search.hip)
+# ----------------------------------------------------------------------------
+BEAM_MAX_R = 16   # rows per call (groups times beams): the decode step's batch, as SAMPLE_MAX_B
+
+
+def _beam_limits():
+    if _lib.lib is None:
+        return 0, 0
+    return _lib.lib.pha_beam_search_max_v(), _lib.lib.pha_beam_search_max_k()
+
+
+BEAM_MAX_V, BEAM_MAX_K = _beam_limits()   # the kernel's vocabulary and beam limits (0: library not built)
+
+
+def _beam_check(logits, cum, finished, lengths, beam_size, cache_indirection, time_step):
+    """the argument errors of beam_search_step, the same on every path (each names its argument)"""
+    fn = "beam_search_step"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{fn}: logits must be a 2-D tensor [R, V]")
+    if logits.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise ValueError(f"{fn}: logits are {logits.dtype}; bfloat16, float16 or float32 expected")
+    R, V = logits.shape
+    if R < 1 or V < 2:
+        raise ValueError(f"{fn}: logits are [{R}, {V}]; at least one row and two columns expected")
+    if logits.stride(1) != 1 or logits.stride(0) < V:
+        raise ValueError(f"{fn}: logits strides {tuple(logits.stride())}: the last must be 1 and the first >= V={V}")
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or beam_size < 1 or beam_size > V \
+            or R % beam_size:
+        raise ValueError(f"{fn}: beam_size={beam_size!r} must be an int in [1, V={V}] that divides the {R} rows")
+    dev = logits.device
+    for name, t, dt in (("cum", cum, torch.float32), ("finished", finished, torch.uint8),
+                        ("lengths", lengths, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (R,) or t.device != dev \
+                or not t.is_contiguous():
+            raise ValueError(f"{fn}: {name} must be a contiguous {dt} [{R}] tensor on {dev}")
+    t = cache_indirection
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != R or t.shape[1] < 1 \
+            or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{fn}: cache_indirection must be a contiguous int32 [{R}, max_seq] tensor on {dev}")
+    if isinstance(time_step, torch.Tensor):
+        if time_step.dtype != torch.int32 or time_step.device != dev or time_step.numel() not in (1, R) \
+                or not time_step.is_contiguous():
+            raise ValueError(f"{fn}: a tensor time_step must be contiguous int32 on {dev} with one element or one per "
+                             f"row ({R})")
+    elif isinstance(time_step, bool) or not isinstance(time_step, int) or not 0 <= time_step < t.shape[1]:
+        raise ValueError(f"{fn}: time_step {time_step!r} outside the table's [0, {t.shape[1]})")
+
+
+def _beam_reject(logits, beam_size):
+    """why the kernels cannot take arguments that passed _beam_check, or None"""
+    if not logits.is_cuda:
+        return f"logits are on {logits.device}, not a GPU"
+    if logits.dtype not in (torch.bfloat16, torch.float16):
+        return f"logits are {logits.dtype}; the kernel takes bfloat16 or float16"
+    if logits.shape[0] > BEAM_MAX_R:
+        return f"R={logits.shape[0]} rows are above the kernel's {BEAM_MAX_R}"
+    if logits.shape[1] > BEAM_MAX_V:
+        return f"V={logits.shape[1]} is above the kernel's {BEAM_MAX_V} (one row of keys plus the histograms in LDS)"
+    if beam_size > BEAM_MAX_K:
+        return f"beam_size={beam_size} is above the kernel's {BEAM_MAX_K}"
+    if logits.data_ptr() % 2:
+        return "logits are not 2-byte aligned"
+    return None
+
+
+def beam_search_step_excluded(R, V, beam_size):
+    """(R, V, K) classes that lost to the composite in tools/bench_generate.py --beams and stay on it
+    by default (a policy, not a fallback). None: see profiles/generate/README.md."""
+    return False
+
+
+def beam_search_step_supported(logits, cum, finished, lengths, beam_size, cache_indirection, time_step):
+    """what the beam-step kernels take: bf16 / fp16 logits [R, V] on a GPU with 1 <= R <= 16,
+    2 <= V <= BEAM_MAX_V (65,536), unit inner stride and a row stride of at least V; 1 <= beam_size <= 16
+    dividing R; float32 cum [R], uint8 finished [R], int32 lengths [R], a contiguous int32 table
+    [R, max_seq] and an int32 time step (int, one element or [R]). float32 logits are not taken."""
+    if _lib.lib is None:
+        return False
+    try:
+        _beam_check(logits, cum, finished, lengths, beam_size, cache_indirection, time_step)
+    except ValueError:
+        return False
+    return _beam_reject(logits, beam_size) is None \
+        and not beam_search_step_excluded(logits.shape[0], logits.shape[1], beam_size)
+
+
+def beam_search_step_why_not(logits, cum, finished, lengths, beam_size, cache_indirection, time_step):
+    """the reason the beam-step kernels would reject these arguments, for the fallback log"""
+    if _lib.lib is None:
+        return "kernel library not loaded"
+    try:
+        _beam_check(logits, cum, finished, lengths, beam_size, cache_indirection, time_step)
+    except ValueError as e:
+        return str(e)
+    return _beam_reject(logits, beam_size) or "supported"
+
+
+def _beam_ts_rows(time_step, R, device):
+    """the step of every row as int32 [R] on ``device`` (no host sync)"""
+    if isinstance(time_step, torch.Tensor):
+        return time_step if time_step.numel() == R else time_step.reshape(1).expand(R).contiguous()
+    return torch.full((R,), int(time_step), dtype=torch.int32, device=device)
+
+
+def _beam_search_step_composite(logits, cum, finished, lengths, eos_token_id, beam_size, cache_indirection, time_step):
+    """beam_search_step's contract in plain torch (any device, any float dtype, any R; no host sync):
+    a stable descending sort of each group's flattened fp32 totals"""
+    R, V = logits.shape
+    K, G = int(beam_size), R // int(beam_size)
+    dev, eos = logits.device, int(eos_token_id)
+    ninf = float("-inf")
+    lp = torch.log_softmax(logits.float(), -1)
+    fin = finished.bool()
+    done = torch.full((V,), ninf, dtype=torch.float32, device=dev)
+    if 0 <= eos < V:
+        done[eos] = 0.0
+    lp = torch.where(fin[:, None], done[None, :], lp)
+    total = (cum[:, None] + lp).reshape(G, K * V)
+    vals, idx = torch.sort(total, dim=-1, descending=True, stable=True)
+    vals, idx = vals[:, :K].reshape(R), idx[:, :K].reshape(R)
+    parent = (idx // V).to(torch.int32)
+    dead = vals == ninf
+    tok = torch.where(dead, eos, idx % V)
+    prow = (torch.arange(G, device=dev).repeat_interleave(K) * K + parent).long()
+    pfin = fin[prow]
+    new_len = lengths[prow] + (~pfin).to(torch.int32)
+    ts = _beam_ts_rows(time_step, R, dev)
+    max_seq = cache_indirection.shape[1]
+    ok = ((ts >= 0) & (ts < max_seq))[:, None]
+    t = torch.arange(max_seq, device=dev, dtype=torch.int32)[None, :]
+    new = torch.where(t < ts[:, None], cache_indirection[prow],
+                      torch.where(t == ts[:, None], parent[:, None], cache_indirection))
+    cache_indirection.copy_(torch.where(ok, new, cache_indirection))
+    logprob = lp.reshape(G, K * V).gather(1, idx.reshape(G, K)).reshape(R).masked_fill(dead, ninf)
+    cum.copy_(vals)
+    finished.copy_((pfin | dead | (tok == eos)).to(torch.uint8))
+    lengths.copy_(new_len)
+    return tok, parent, logprob
+
+
+def beam_search_step(logits, cum, finished, lengths, eos_token_id, beam_size, cache_indirection, time_step):
+    """One beam-search step over ``logits`` [R, V], R = groups * ``beam_size`` rows, row b * K + k being
+    beam k of batch item b. Returns (token int64 [R], parent int32 [R], logprob fp32 [R]: the token's
+    log probability under its parent row, 0 for the EOS a finished beam repeats) and replaces ``cum`` (fp32 [R],
+    the beams' cumulative log probabilities), ``finished`` (uint8 [R]) and ``lengths`` (int32 [R]) in
+    place.
+
+    ``lp = log_softmax(logits)`` in fp32; a finished row has lp = 0 at ``eos_token_id`` and -inf
+    elsewhere. ``total[b, k * V + v] = cum[b * K + k] + lp[b * K + k, v]``; the K largest totals of a
+    group are taken in descending order, equal totals in ascending flat index (lower beam, then lower
+    token). Pick j becomes new beam j: token ``idx % V``, parent ``idx // V`` (a beam number in
+    [0, K)), cum the total, finished ``finished[parent] | (token == eos)``, length ``lengths[parent] +
+    !finished[parent]``. A pick whose total is -inf (only where a group has fewer than K finite
+    totals) carries token ``eos_token_id``, log probability -inf and is finished; the other outputs follow the same rules.
+    The first step of a search passes ``cum = [0, -inf, ...]`` per group, so all K picks continue beam 0.
+
+    ``cache_indirection`` (int32 [R, max_seq], the table of ``decode_attention``) is re-ordered in
+    place for the step ``time_step`` (int, int32 tensor of one element, or [R]): for t < time_step,
+    ``table'[r, t] = table[group row parent[r], t]``, then ``table'[r, time_step] = parent[r]``;
+    nothing above is touched and ``time_step`` is not advanced.
+
+    On a GPU, bf16 / fp16 logits with R <= 16, V <= 65,536 and beam_size <= 16 run on two kernel
+    launches (csrc/kernels/beam_search.hip) without a host sync. float32 logits, the CPU and anything
+    else the kernels reject run the same contract in plain torch (``_beam_search_step_composite``; on
+    a GPU recorded as a fallback). PHA_BEAM_KERNEL=0 forces the composite."""
+    import os
+    _beam_check(logits, cum, finished, lengths, beam_size, cache_indirection, time_step)
+    R, V = logits.shape
+    K = int(beam_size)
+    use = logits.is_cuda and os.environ.get("PHA_BEAM_KERNEL", "1") != "0"
+    if use and not beam_search_step_excluded(R, V, K):
+        why = "kernel library not loaded" if _lib.lib is None else _beam_reject(logits, K)
+        if why is None:
+            dev = logits.device
+            tok = torch.empty((R,), dtype=torch.int64, device=dev)
+            parent = torch.empty((R,), dtype=torch.int32, device=dev)
+            logprob = torch.empty((R,), dtype=torch.float32, device=dev)
+            cand_lp = torch.empty((R, BEAM_MAX_K), dtype=torch.float32, device=dev)
+            cand_tok = torch.empty((R, BEAM_MAX_K), dtype=torch.int32, device=dev)
+            ts = _beam_ts_rows(time_step, R, dev)
+            _check(_L().pha_beam_search_step(_DT[logits.dtype], _ptr(logits), logits.stride(0), _ptr(cum),
+                                             _ptr(finished), _ptr(lengths), _ptr(tok), _ptr(parent),
+                                             _ptr(logprob), _ptr(cache_indirection), _ptr(ts), _ptr(cand_lp), _ptr(cand_tok), R, V, K,
+                                             int(eos_token_id), cache_indirection.shape[1], _stream(logits)),
+                   "beam_search_step")
+            return tok, parent, logprob
+        from . import fallback
+        fallback.note("beam_search_step", why + " -> torch composite")
+    return _beam_search_step_composite(logits, cum, finished, lengths, eos_token_id, beam_size, cache_indirection,
+                                       time_step)

@@ -19,8 +19,15 @@ against the composite that PHA_DECODE_ATTN=0 keeps.
     "within" is the project's gating rule: the medians differ by no more than the larger min - max
     spread of the two arms.
 
+(d) with --beam: the beam-indirect form (pha_decode_attn_beam) at B = 8 rows in groups of K = 4 and the
+    shapes of (a), every arm one captured graph over the 24 caches. (iii) the beam kernel with the
+    identity table against the per-row kernel: the price of the table. (iv) the beam kernel with a
+    scrambled table against re-ordering the live part of every cache row with torch and then the
+    per-row kernel: the design the table replaces.
+
 Prints markdown tables. Usage: python tools/bench_decode_attn.py [--rounds 7] [--iters 960] [--skip-model]
                                                                  [--rows [--parent-lib NAME] [--skip-attention]]
+                                                                 [--beam]
 """
 import argparse
 import ctypes
@@ -202,6 +209,69 @@ def bench_rows(rounds, iters, parent_lib):
     print()
 
 
+def bench_beam(rounds, iters, K=4):
+    """part (d): the beam-indirect form at B rows in groups of K. (iii) identity table against
+    pha_decode_attn_rows: the price of the table. (iv) scrambled table against gathering the caches with
+    torch and then pha_decode_attn_rows: the design the table replaces."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    qkv = torch.randn(B, 3, H, D, device="cuda", generator=g).bfloat16()
+    qb = (torch.randn(3, H, D, device="cuda", generator=g) * 0.1).bfloat16()
+    caches = [torch.randn(2, B, H, MAX_SEQ, D, device="cuda", generator=g).bfloat16() for _ in range(LAYERS)]
+    reps = max(4, iters // LAYERS)
+    ident = (torch.arange(B, device="cuda", dtype=torch.int32) % K)[:, None].expand(B, MAX_SEQ).contiguous()
+    scram = torch.randint(0, K, (B, MAX_SEQ), device="cuda", generator=g, dtype=torch.int32)
+    src = (torch.arange(B, device="cuda") // K * K)[:, None] + scram.long()          # [B, MAX_SEQ] cache rows
+    pos = torch.arange(MAX_SEQ, device="cuda")[None, :]
+
+    def us(t):
+        return f"{t[0] * 1e3 / LAYERS:.2f} ({t[1] * 1e3 / LAYERS:.2f} - {t[2] * 1e3 / LAYERS:.2f})"
+
+    def verdict(new, old):
+        margin = max(new[2] - new[1], old[2] - old[1])
+        d = (new[0] - old[0]) * 1e3 / LAYERS
+        return f"{d:+.2f} us, margin {margin * 1e3 / LAYERS:.2f}: " + ("within" if abs(new[0] - old[0]) <= margin else
+                                                                         "slower" if d > 0 else "faster")
+
+    def capture(fn):
+        fn(0)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(LAYERS):
+                fn(i)
+        return gr
+
+    def gather_then_rows(cache, rows, ts):
+        """what a beam step without the table does per layer: re-order the live part of every cache row,
+        then the per-row kernel"""
+        live = cache[:, :, :, :ts]
+        cache[:, :, :, :ts] = live[:, src[:, :ts], :, pos[:, :ts]].permute(2, 0, 3, 1, 4)
+        return hip.decode_attention(qkv, qb, cache, rows)
+
+    print(f"### (d) beam-indirect form: B={B} rows, K={K}, H={H} D={D} max_seq={MAX_SEQ} bf16, graph replay over "
+          f"{LAYERS} caches, us per call, median of {rounds} rounds x {reps} replays (min - max)\n")
+    print("| ts | per-row kernel | beam kernel, identity table | (iii) table - none | beam kernel, scrambled table | "
+          "torch gather + per-row kernel | (iv) ratio | identity output |")
+    print("|---|---|---|---|---|---|---|---|")
+    for ts in (127, 1023, 2047):
+        rows = torch.full((B,), ts, dtype=torch.int32, device="cuda")
+        c = [caches[0].clone() for _ in range(2)]
+        o0 = hip.decode_attention(qkv, qb, c[0], rows)
+        o1 = hip.decode_attention(qkv, qb, c[1], rows, cache_indirection=ident, beam_size=K)
+        same = torch.equal(o0.view(torch.int16), o1.view(torch.int16)) and torch.equal(c[0].view(torch.int16),
+                                                                                         c[1].view(torch.int16))
+        fns = [lambda i: hip.decode_attention(qkv, qb, caches[i % LAYERS], rows),
+               lambda i: hip.decode_attention(qkv, qb, caches[i % LAYERS], rows, cache_indirection=ident, beam_size=K),
+               lambda i: hip.decode_attention(qkv, qb, caches[i % LAYERS], rows, cache_indirection=scram, beam_size=K),
+               lambda i: gather_then_rows(caches[i % LAYERS], rows, ts)]
+        graphs = [capture(fn) for fn in fns]
+        res = alternate([lambda _, gr=gr: gr.replay() for gr in graphs], reps, rounds)
+        print(f"| {ts} | {us(res[0])} | {us(res[1])} | {verdict(res[1], res[0])} | {us(res[2])} | {us(res[3])} | "
+              f"{res[3][0] / res[2][0]:.1f}x | {'bitwise equal' if same else 'DIFFERS'} |")
+        del graphs
+    print()
+
+
 def bench_model(rounds, iters):
     E, DFF, ts = H * D, 4 * H * D, 1023
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -257,6 +327,7 @@ def main():
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--skip-attention", action="store_true")
     ap.add_argument("--rows", action="store_true", help="part (c): per-row time steps")
+    ap.add_argument("--beam", action="store_true", help="part (d): the beam-indirect form")
     ap.add_argument("--parent-lib", default=None,
                     help="file name under paddle_hackathon_amd/_C/ of a library built from the parent commit's "
                          "decode_attn.hip, for the scalar arm of part (c)")
@@ -269,6 +340,8 @@ def main():
             bench_attention(a.rounds, a.iters)
         if a.rows:
             bench_rows(a.rounds, a.iters, a.parent_lib)
+        if a.beam:
+            bench_beam(a.rounds, a.iters)
     if not a.skip_model:
         bench_model(a.rounds, max(8, a.iters // LAYERS))
 

@@ -12,11 +12,18 @@
 (d) with --ragged: the same model, B = 8, 128 new tokens, greedy, replayed from the graph: prompts of
     16..128 tokens (``seq_lens``, a time step per row) against all eight at 128.
 
+(e) with --beams K: ops.hip.beam_search_step on the kernels (csrc/kernels/beam_search.hip) against the torch
+    composite that PHA_BEAM_KERNEL=0 keeps, bf16 logits [R, 50304] at R = 4 / 8 / 16 rows in groups of K, each
+    arm one captured graph of 8 calls; and
+(f) beam-search generation at GPT-3 1.3B, bf16, B = 2, K beams, prompt 128, 128 new tokens: replayed from the
+    captured graph and eager, each with PHA_BEAM_KERNEL=0 and 1 (ms per call, per token, tokens/s per beam row).
+
 The arms alternate in one process; medians over the rounds with min - max. "stays" is the rule of
 profiles/decode_gemm/README.md: the kernel's median is below the other arm's by more than the larger
 min - max spread of the two.
 
 Prints markdown tables. Usage: python tools/bench_generate.py [--rounds 7] [--iters 20] [--skip-model] [--ragged]
+                                                     [--beams 4]
 """
 import argparse
 import os
@@ -195,6 +202,79 @@ def bench_ragged(rounds, B=8, prompt=128, new=128):
     print()
 
 
+def bench_beam_step(rounds, iters, K):
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    max_seq, ts = 256, 200
+    print(f"### (e) beam_search_step, bf16 logits [R, {V}] (row stride {V + 8}), K = {K}, table [R, {max_seq}] at "
+          f"step {ts}, {CALLS} calls per graph, us per call, median of {rounds} rounds x {iters} replays (min - max)\n")
+    print("| R | kernels | composite | speedup | stays | same picks |")
+    print("|---|---|---|---|---|---|")
+    for R in (4, 8, 16):
+        if R % K:
+            continue
+        logits = [(torch.randn(R, V + 8, device="cuda", generator=gen) * 2).bfloat16()[:, :V] for _ in range(CALLS)]
+        state = lambda: (-torch.rand(R, device="cuda", generator=gen) * 5, torch.zeros(R, dtype=torch.uint8, device="cuda"),
+                         torch.ones(R, dtype=torch.int32, device="cuda"),
+                         torch.randint(0, K, (R, max_seq), device="cuda", generator=gen, dtype=torch.int32))
+        tsr = torch.full((R,), ts, dtype=torch.int32, device="cuda")
+        cum0, fin0, len0, tab0 = state()
+        sn, so = [t.clone() for t in (cum0, fin0, len0, tab0)], [t.clone() for t in (cum0, fin0, len0, tab0)]
+        pn = hip.beam_search_step(logits[0], sn[0], sn[1], sn[2], -1, K, sn[3], tsr)
+        po = hip._beam_search_step_composite(logits[0], so[0], so[1], so[2], -1, K, so[3], tsr)
+        same = torch.equal(pn[0], po[0]) and torch.equal(pn[1], po[1]) and torch.equal(sn[3], so[3])
+
+        def new(i):
+            return hip.beam_search_step(logits[i], sn[0], sn[1], sn[2], -1, K, sn[3], tsr)
+
+        def old(i):
+            return hip._beam_search_step_composite(logits[i], so[0], so[1], so[2], -1, K, so[3], tsr)
+
+        graphs = [capture(f) for f in (new, old)]
+        tn, to = alternate([lambda _, g=g: g.replay() for g in graphs], iters, rounds)
+        print(f"| {R} | {us(tn)} | {us(to)} | {to[0] / tn[0]:.1f}x | {stays(tn, to)} | {'yes' if same else 'no'} |")
+        del graphs
+    print()
+
+
+def bench_beam_generate(rounds, K, B=2, prompt=128, new=128):
+    import paddle_hackathon_amd as paddle
+    from paddle_hackathon_amd.models import GPTForPretraining, GPTGenerator, gpt_config
+    paddle.set_device("gpu:0")
+    paddle.seed(0)
+    model = paddle.amp.decorate(GPTForPretraining(gpt_config("gpt3-1.3b")), level="O2", dtype="bfloat16")
+    model.eval()
+    ids = torch.randint(0, V, (B, prompt), device="cuda", generator=torch.Generator(device="cuda").manual_seed(2))
+    gens = {"0": GPTGenerator(model), "1": GPTGenerator(model)}   # a captured graph keeps the switch it was captured with
+
+    def arm(switch, graph):
+        def fn():
+            os.environ["PHA_BEAM_KERNEL"] = switch
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out, _ = gens[switch].generate(ids, new, use_graph=graph, decode_strategy="beam_search", num_beams=K)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, out._t
+        return fn
+
+    arms = [("graph, PHA_BEAM_KERNEL=0 (composite)", arm("0", True)), ("graph, PHA_BEAM_KERNEL=1", arm("1", True)),
+            ("eager, PHA_BEAM_KERNEL=0 (composite)", arm("0", False)), ("eager, PHA_BEAM_KERNEL=1", arm("1", False))]
+    outs = [fn()[1] for _, fn in arms]   # warm-up: captures the graphs
+    samples = [[] for _ in arms]
+    for _ in range(rounds):
+        for s, (_, fn) in zip(samples, arms):
+            s.append(fn()[0])
+    os.environ.pop("PHA_BEAM_KERNEL", None)
+    print(f"### (f) generate, beam search, GPT-3 1.3B bf16, B = {B}, K = {K} ({B * K} rows), prompt {prompt}, {new} new "
+          f"tokens, whole call (prefill over the {B} prompts included), median of {rounds} rounds (min - max)\n")
+    print("| path | ms per call | ms per token | row tokens/s |")
+    print("|---|---|---|---|")
+    for (label, _), s in zip(arms, samples):
+        med, lo, hi = statistics.median(s), min(s), max(s)
+        print(f"| {label} | {med:.1f} ({lo:.1f} - {hi:.1f}) | {med / new:.3f} | {B * K * new / med * 1e3:.0f} |")
+    same = all(torch.equal(outs[0], o) for o in outs[1:])
+    print(f"\nthe four arms return {'the same' if same else 'different'} tokens\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -203,6 +283,7 @@ def main():
     ap.add_argument("--skip-lm-head", action="store_true")
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--ragged", action="store_true", help="part (d): prompts of different lengths")
+    ap.add_argument("--beams", type=int, default=0, help="parts (e) and (f): beam search with this many beams")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate needs a GPU")
@@ -216,6 +297,10 @@ def main():
             bench_generate(a.rounds)
         if a.ragged:
             bench_ragged(a.rounds)
+        if a.beams:
+            bench_beam_step(a.rounds, a.iters, a.beams)
+            if not a.skip_model:
+                bench_beam_generate(a.rounds, a.beams)
 
 
 if __name__ == "__main__":
