@@ -1645,6 +1645,370 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int jb = 0; jb < 8; jb += 2) store_pair(acc[i][jb], acc[i][jb + 1], i, jb);
 }
 
+// ================================================================================================
+// BN192: the TN early-release kernel on 256 x 192 x 64 tiles (EPI_BN field = 1). A weight gradient
+// whose 256 x 256 tiles fill 3/4 of the CUs (GPT-3 1.3B's qkv dW, 2048 x 6144: 192 tiles on 256
+// CUs) has exactly one round of 256 x 192 items instead — no idle quarter, no split-K slabs, no
+// reduce pass. Same v_mfma_f32_16x16x32, same LDS-DMA staging, same early-release schedule and
+// overlapped epilogue as gemm4p_kernel<T, AKO, BKO, ..., EARLY, LV 40 (PIN + SPREAD)>, and the
+// same K order per output element and per column-sum lane: results are bitwise those of the 256 form.
+//
+// Wave (wr, wc) owns 128 x 96: acc[8][6] (192 AGPRs),
+//   acc[i][j][e] = C[wr*128 + i*16 + fr][wc*96 + j*16 + 4fk + e]; tiles j, j + 1 pair in the store.
+// A k-half is 48 MFMAs = 12 groups of 4; group s runs the linear tile indices t = 4s..4s+3 with
+// (i, j) = (t / 6, t % 6), which are exactly the pairs 2s and 2s + 1 of the epilogue (pair p: row
+// block p / 3, columns 2 (p % 3) and + 1), so an epilogue phase stores 2 pairs per group, 24 per tile.
+//
+// LDS stage: the A image as in gemm4p_kernel (32 KB: two 128-column halves of 64 k-rows x 256 B),
+// then the B image: 64 k-rows x 192 columns = 384-B rows, 24 KB, 24 one-KiB DMA pieces (6 per wave;
+// piece g holds the lane-linear 16-B chunks 64g..64g+63 of the image, chunk c = k-row c / 24, slot
+// c % 24). A 384-B row pitch is 32 banks mod 64, as the 128-B pitch of tn_mask's second form: a
+// transposed fragment read touches k-rows {8fk + q} (+ 4 for the high half), 32 B each, and with
+// slot ^= tn_mask(row, 128) (bits 1-2 of the slot from row bits 1 and 3, inside an 8-slot group,
+// 24 = 3 groups) the 8 rows of each half-wave cover the 64 banks once (row bit 0 moves by the pitch).
+//
+// Counted waits, re-derived for 12 groups, 14 fragment reads (8 A + 6 B) and 14 DMAs (8 A + 6 B
+// pieces per wave and K-tile) — in vmcnt's issue order, stores included:
+//   * phase A (k-half 0's MFMAs): the 14 reads of k-half 1 over groups 0-5 (2, 2, 3, 2, 2, 3), then
+//     lgkmcnt(0) + barrier at group N_RELG = 6 release the K-tile's buffer (half-way, as RELG 8 of
+//     16), and DMAs 0-5 of the next-next K-tile go out one per group in groups 6-11 (N_SNA = 6);
+//   * A/B boundary: the previous K-tile's DMA set must have landed. Younger than its last DMA are
+//     phase A's N_SNA = 6 DMAs -> vmcnt(6); in a tile's first K-tile also the epilogue's 24 stores
+//     -> vmcnt(30). (A column-sum build's 2 stores per item fall between that set and phase A's
+//     DMAs: two more younger operations, which only makes the counted wait stricter.)
+//   * phase B (k-half 1's MFMAs): DMAs 6-13 two per three groups over all 12 groups (the SPREAD
+//     placement: d in [6 + 8s/12, 6 + 8(s+1)/12)), and the next K-tile's k-half-0 reads two per group
+//     over groups 0-6 in the order the next phase A consumes them (A0, B0-5, A1-7).
+//   Every DMA has >= 12 groups (48 MFMAs) of cover before the boundary that waits for it.
+// ================================================================================================
+constexpr int EPI_BN_SHIFT = 10;   // bits 10-11 of epi: tile width (0: 256, 1: 192, else refused)
+constexpr int N_BN = 192;
+constexpr int N_BROW = N_BN * 2;             // B image row pitch (bytes)
+constexpr int N_BOPB = 64 * N_BROW;          // B image (24 KB)
+constexpr int N_STAGE = OPB + N_BOPB;        // A image, B image (56 KB)
+constexpr int N_SMEM = 2 * N_STAGE;
+constexpr int N_NG = 12;                     // MFMA groups per k-half
+constexpr int N_NRD = 14, N_NDMA = 14;       // fragment reads per k-half, DMAs per wave and K-tile
+constexpr int N_RELG = 6, N_SNA = N_NG - N_RELG;
+constexpr int N_NST = 24;                    // stores of an epilogue phase
+static_assert(N_SNA + N_NST <= 63, "the counted wait fits vmcnt");
+static_assert(N_STAGE % 1024 == 0 && N_BOPB == 24 * 1024, "1-KiB DMA pieces");
+
+template <typename T, bool CS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm4p192_kernel(Args p) {
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[N_SMEM];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wid >> 1, wc = wid & 1;
+  const int M = p.M, N = p.N;
+  const int nk = p.K >> 6;
+
+  Sched sc;
+  sc.tiles_m = (M + 255) >> 8;
+  sc.tiles_n = (N + N_BN - 1) / N_BN;
+  sc.splits = 1;
+  sc.per_batch = sc.tiles_m * sc.tiles_n;
+  sc.total = sc.per_batch;
+  sc.G = gridDim.x;
+  sc.gm = p.group_m;
+  {
+    const int bid = blockIdx.x, G = gridDim.x;
+    const int q8 = G >> 3, r8 = G & 7, xcd = bid & 7;
+    sc.pos = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    if (r8 == 0) {
+      const int qt = sc.total >> 3, rt = sc.total & 7;
+      sc.c0 = (xcd < rt ? xcd * (qt + 1) : rt * (qt + 1) + (xcd - rt) * qt) + (bid >> 3);
+      sc.c1 = sc.c0 - (bid >> 3) + qt + (xcd < rt ? 1 : 0);
+      sc.step = q8;
+    } else {
+      sc.c0 = sc.pos;
+      sc.c1 = sc.total;
+      sc.step = G;
+    }
+  }
+  if (!sc.valid(0)) return;
+
+  // ---- staging cursor (round rs, k-tile ks): per-lane DMA offsets of the cursor's tile ------------
+  unsigned aoff[8], boff[6];
+  const char* abase;
+  const char* bbase;
+  int rs = 0, ks = 0;
+  const size_t astep = (size_t)64 * p.lda * 2, bstep = (size_t)64 * p.ldb * 2;
+  const unsigned lds0 = lds_u32(smem);
+  auto set_tile = [&](int r) {
+    int tm, tn, slice, bi;
+    sc.tile(r, tm, tn, slice, bi);
+    const int m0 = tm << 8, n0 = tn * N_BN;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {   // A: gemm4p_kernel's K-outer image (columns clamped into the operand)
+      const int g = wid * 8 + u;
+      const int half = g >> 4, krow = (g & 15) * 4 + (lane >> 4);
+      const int src = (lane & 15) ^ tn_mask(krow, 256);
+      const int idx = min(half * 128 + src * 8, M - m0 - 8);
+      aoff[u] = ((unsigned)krow * (unsigned)p.lda + (unsigned)idx) * 2u;
+    }
+#pragma unroll
+    for (int u = 0; u < 6; ++u) {   // B: chunk c of the image = (k-row c / 24, slot c % 24)
+      const int c = (wid * 6 + u) * 64 + lane;
+      const int krow = c / 24, slot = c - krow * 24;
+      const int src = slot ^ tn_mask(krow, 128);
+      const int idx = min(src * 8, N - n0 - 8);
+      boff[u] = ((unsigned)krow * (unsigned)p.ldb + (unsigned)idx) * 2u;
+    }
+    abase = static_cast<const char*>(p.a) + (size_t)m0 * 2;
+    bbase = static_cast<const char*>(p.b) + (size_t)n0 * 2;
+  };
+  const char* st_a = nullptr;
+  const char* st_b = nullptr;
+  bool st_on = false;
+  int st_buf = 0;
+  // (past the last tile the cursor stays on the last K-tile: DMAs into a buffer nothing reads)
+  auto stage_begin = [&](int buf) {
+    st_on = sc.valid(rs);
+    const int kk = st_on ? ks : nk - 1;
+    st_a = abase + (size_t)kk * astep;
+    st_b = bbase + (size_t)kk * bstep;
+    st_buf = buf;
+  };
+  auto stage_one = [&](int d) {   // DMA d (0..13): A, B alternating for pieces 0-5, then A pieces 6, 7
+    const unsigned st = lds0 + st_buf * N_STAGE;
+    if (d >= 12) glds_sv(aoff[d - 6], st_a, st + (wid * 8 + d - 6) * 1024);
+    else if (d & 1) glds_sv(boff[d >> 1], st_b, st + OPB + (wid * 6 + (d >> 1)) * 1024);
+    else glds_sv(aoff[d >> 1], st_a, st + (wid * 8 + (d >> 1)) * 1024);
+  };
+  auto stage_end = [&]() {
+    if (!st_on) return;
+    if (++ks == nk) {
+      ks = 0;
+      ++rs;
+      if (sc.valid(rs)) set_tile(rs);
+    }
+  };
+
+  const int fr = lane & 15, fk = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
+  auto readA = [&](int buf, int kh, int i) -> uint4 {
+    return tn_frag<256>(smem + buf * N_STAGE + wr * 16384, kh * 32 + 8 * fk, i * 16, tq, tp);
+  };
+  auto readB = [&](int buf, int kh, int j) -> uint4 {   // tn_frag on the 384-B rows (see the header)
+    const unsigned char* img = smem + buf * N_STAGE + OPB;
+    const int ch = ((wc * 96 + j * 16) >> 3) + (tp >> 1);
+    const int ra = kh * 32 + 8 * fk + tq, rb = ra + 4;
+    const uint2 lo = tr16(img + ra * N_BROW + ((ch ^ tn_mask(ra, 128)) << 4) + 8 * (tp & 1));
+    const uint2 hi = tr16(img + rb * N_BROW + ((ch ^ tn_mask(rb, 128)) << 4) + 8 * (tp & 1));
+    return uint4{lo.x, lo.y, hi.x, hi.y};
+  };
+  // fragment read r of a k-half in consumption order: A0, B0-5, A1-7
+  auto read_one = [&](int r, uint4 (&na)[8], uint4 (&nb)[6], int rbuf, int rkh) {
+    if (r == 0) na[0] = readA(rbuf, rkh, 0);
+    else if (r <= 6) nb[r - 1] = readB(rbuf, rkh, r - 1);
+    else na[r - 6] = readA(rbuf, rkh, r - 6);
+  };
+
+  // ---- epilogue geometry: after the pair swap a lane holds 8 consecutive output columns starting
+  // at wc*96 + (pair base)*16 + (fk & 1)*16 + (fk >> 1)*8 of output row wr*128 + (row block)*16 + fr
+  const int ldc2 = p.ldc * 2;
+  const int wrow = wr * 128;
+  const int lcol = wc * 96 + (fk & 1) * 16 + (fk >> 1) * 8;
+  const unsigned lane_voff = (unsigned)(fr * ldc2 + lcol * 2);
+  const char* e_base = static_cast<const char*>(p.c);
+  int e_rows = 0, e_cols = 0;   // (no previous tile yet: zero rows, the first epilogue phase's stores are dropped)
+  auto set_epi = [&](int r) {
+    int tm, tn, slice, bi;
+    sc.tile(r, tm, tn, slice, bi);
+    const int r0 = tm << 8, c0 = tn * N_BN;
+    e_base = static_cast<const char*>(p.c) + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
+    e_rows = M - r0 - wrow;
+    e_cols = N - c0;
+  };
+  // pair (cb, cb + 1) of row block rb: gemm4p_kernel's store_pair without an epilogue function (rows
+  // past the output dropped by the buffer's size, column groups past N by an offset past any size)
+  auto store_pair = [&](const f32x4& x0, const f32x4& x1, int rb, int cb) {
+    float v0[4], v1[4];
+    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
+                 "v_accvgpr_read_b32 %3, %7"
+                 : "=v"(v0[0]), "=v"(v0[1]), "=v"(v0[2]), "=v"(v0[3]) : "a"(x0[0]), "a"(x0[1]), "a"(x0[2]), "a"(x0[3]));
+    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
+                 "v_accvgpr_read_b32 %3, %7"
+                 : "=v"(v1[0]), "=v"(v1[1]), "=v"(v1[2]), "=v"(v1[3]) : "a"(x1[0]), "a"(x1[1]), "a"(x1[2]), "a"(x1[3]));
+    const int nbytes = __builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
+    const unsigned voff = (lcol + cb * 16 < e_cols) ? lane_voff : 0x80000000u;
+    const unsigned q00 = pk<T>(v0[0], v0[1]), q01 = pk<T>(v0[2], v0[3]);
+    const unsigned q10 = pk<T>(v1[0], v1[1]), q11 = pk<T>(v1[2], v1[3]);
+    const auto s0 = __builtin_amdgcn_permlane16_swap(q00, q10, false, false);
+    const auto s1 = __builtin_amdgcn_permlane16_swap(q01, q11, false, false);
+    const size_t bp = (size_t)(e_base + (size_t)rb * 16 * ldc2);
+    const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp);
+    const unsigned bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        reinterpret_cast<void*>(((size_t)bhi << 32) | blo), (short)0, nbytes, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4v{s0[0], s1[0], s0[1], s1[1]}, rsrc, voff + cb * 32, 0, 2);
+  };
+  auto store_nth = [&](f32x4 (&acc)[8][6], int pr) {   // pair pr (0..23) of the tile
+    store_pair(acc[pr / 3][(pr % 3) * 2], acc[pr / 3][(pr % 3) * 2 + 1], pr / 3, (pr % 3) * 2);
+  };
+
+  f32x4 acc[8][6];
+  uint4 fa0[8], fb0[6], fa1[8], fb1[6];
+  // CS: per-lane column sums of the B fragments (fragment j: column wc*96 + 16j + fr, k-quarter fk)
+  float csum[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+  // one k-half: MODE 0 accumulates, MODE 2 starts a fresh tile (C = 0) and writes the previous tile's
+  // accumulators out right before the MFMAs that overwrite them. REL: phase A (read burst, release,
+  // DMAs 0-5), else phase B (paced reads, DMAs 6-13). CSP: the column-sum dot2s of this k-half.
+  auto phase = [&](auto mode_c, auto rel_c, auto cs_c, uint4 (&ca)[8], uint4 (&cb)[6], uint4 (&na)[8], uint4 (&nb)[6],
+                   int rbuf, int rkh, int stbuf, unsigned onesel) {
+    constexpr int MODE = decltype(mode_c)::value;
+    constexpr bool REL = decltype(rel_c)::value;
+#pragma unroll
+    for (int s = 0; s < N_NG; ++s) {
+      if constexpr (REL) {
+        if (s < N_RELG) {
+#pragma unroll
+          for (int r = s * N_NRD / N_RELG; r < (s + 1) * N_NRD / N_RELG; ++r) read_one(r, na, nb, rbuf, rkh);
+        }
+        if (s == N_RELG) {
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+          bar();
+          stage_begin(stbuf);
+        }
+        if (s >= N_RELG) stage_one(s - N_RELG);
+      } else {
+        if (2 * s < N_NRD) {
+          read_one(2 * s, na, nb, rbuf, rkh);
+          read_one(2 * s + 1, na, nb, rbuf, rkh);
+        }
+#pragma unroll
+        for (int d = N_SNA + s * (N_NDMA - N_SNA) / N_NG; d < N_SNA + (s + 1) * (N_NDMA - N_SNA) / N_NG; ++d) stage_one(d);
+      }
+      if constexpr (MODE == 2) {
+        store_nth(acc, 2 * s);
+        store_nth(acc, 2 * s + 1);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = (4 * s + q) / 6, j = (4 * s + q) % 6;
+        if constexpr (MODE == 0) acc[i][j] = Mf<T>::mma(cb[j], ca[i], acc[i][j]);
+        else mma0<T>(acc[i][j], cb[j], ca[i]);
+      }
+      // CS (branch-free, as gemm4p_kernel's): group s < 6 adds the 8 k-values of B fragment s dotted with
+      // onesel — 1.0 x 2 on the wave row that sums this k-half of this K-tile, 0 on the other
+      if constexpr (decltype(cs_c)::value) {
+        if (s < 6) {
+          csum[s % 6] = dot2sel<T>(cb[s % 6].x, onesel, csum[s % 6]);
+          csum[s % 6] = dot2sel<T>(cb[s % 6].y, onesel, csum[s % 6]);
+          csum[s % 6] = dot2sel<T>(cb[s % 6].z, onesel, csum[s % 6]);
+          csum[s % 6] = dot2sel<T>(cb[s % 6].w, onesel, csum[s % 6]);
+        }
+      } else {
+        (void)onesel;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" ::: "memory");   // PIN: no pass sinks a group's LDS reads out of it
+    }
+  };
+
+  // ---- prologue: K-tiles 0 and 1 of the stream into the two buffers --------------------------------
+  set_tile(0);
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    stage_begin(b);
+#pragma unroll
+    for (int d = 0; d < N_NDMA; ++d) stage_one(d);
+    stage_end();
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  bar();
+#pragma unroll
+  for (int i = 0; i < 8; ++i) fa0[i] = readA(0, 0, i);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) fb0[j] = readB(0, 0, j);
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  using yes = std::true_type;
+  using no = std::false_type;
+  using M0 = std::integral_constant<int, 0>;
+  using M2 = std::integral_constant<int, 2>;
+  using CSY = std::integral_constant<bool, CS>;
+  int s = 0;   // global K-tile step; buffer s & 1
+  for (int r = 0; sc.valid(r); ++r) {
+    // CS: tile row tm sums the item's K-tiles [klo, khi) (its 1/tiles_m of the K range), wave row wr
+    // k-half wr of each — the same ranges and lanes as on the 256 form
+    int klo = 0, khi = 0;
+    if constexpr (CS) {
+      int tm, tn, slice, bi;
+      sc.tile(r, tm, tn, slice, bi);
+      klo = __builtin_amdgcn_readfirstlane(tm * nk / sc.tiles_m);
+      khi = __builtin_amdgcn_readfirstlane((tm + 1) * nk / sc.tiles_m);
+    }
+    auto sel = [&](int k, int h) -> unsigned { return (CS && k >= klo && k < khi && wr == h) ? ONES2<T> : 0u; };
+    {
+      const int buf = s & 1;
+      phase(M2{}, yes{}, CSY{}, fa0, fb0, fa1, fb1, buf, 1, buf, sel(0, 0));
+      asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" :: "n"(N_SNA + N_NST) : "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      bar();
+      set_epi(r);
+      phase(M0{}, no{}, CSY{}, fa1, fb1, fa0, fb0, buf ^ 1, 0, buf, sel(0, 1));
+      stage_end();
+      ++s;
+    }
+    auto ktile = [&](auto cs_c, int k) {
+      const int buf = s & 1;
+      phase(M0{}, yes{}, cs_c, fa0, fb0, fa1, fb1, buf, 1, buf, sel(k, 0));
+      asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" :: "n"(N_SNA) : "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      bar();
+      phase(M0{}, no{}, cs_c, fa1, fb1, fa0, fb0, buf ^ 1, 0, buf, sel(k, 1));
+      stage_end();
+    };
+    if constexpr (CS) {   // the K-tile loop cut at klo / khi: only [klo, khi) carries the dot2s
+      int k = 1;
+      for (; k < klo; ++k, ++s) ktile(no{}, k);
+      for (; k < khi; ++k, ++s) ktile(yes{}, k);
+      for (; k < nk; ++k, ++s) ktile(no{}, k);
+    } else {
+      for (int k = 1; k < nk; ++k, ++s) ktile(no{}, k);
+    }
+    if constexpr (CS) {
+      // the item is done: sum the 4 k-quarters (lanes l, l+16, l+32, l+48) of every fragment with
+      // gemm4p_kernel's swaps on 8 slots, the last two zero: permlane32_swap(f_j, f_j+4) + add, then
+      // permlane16_swap(u_j, u_j+1) + add leave lane row fk with the totals of fragments
+      // f0 = (fk & 1) + (fk >> 1) * 4 and f0 + 2 (fragments 6, 7 do not exist: rows 2, 3 store one)
+      int tm, tn, slice, bi;
+      sc.tile(r, tm, tn, slice, bi);
+      float u[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float x0 = csum[j], x1 = j + 4 < 6 ? csum[j + 4] : 0.f;
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
+        u[j] = x0 + x1;
+      }
+      float w[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float x0 = u[2 * j], x1 = u[2 * j + 1];
+        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
+        w[j] = x0 + x1;
+      }
+#pragma unroll
+      for (int j = 0; j < 6; ++j) csum[j] = 0.f;
+      const int f0 = (fk & 1) + (fk >> 1) * 4;
+      float* row = static_cast<float*>(p.aux) + (size_t)(tm * 2 + wr) * N;
+      const int c0 = tn * N_BN + wc * 96 + 16 * f0 + fr;
+      if (c0 < N) row[c0] = w[0];
+      if (fk < 2 && c0 + 32 < N) row[c0 + 32] = w[1];
+    }
+  }
+  // last tile: stores only (after the cursor's trailing DMAs have landed)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int pr = 0; pr < N_NST; ++pr) store_nth(acc, pr);
+}
+
 template <typename T, bool BIAS, bool E>
 int launch_e(const Args& a, int ako, int bko, int trans, int grid, hipStream_t st) {
   if (a.splits > 1) {   // TN only (weight gradients)
@@ -1749,6 +2113,14 @@ int launch_e(const Args& a, int ako, int bko, int trans, int grid, hipStream_t s
   return (int)hipGetLastError();
 }
 
+// the 256 x 192 form: TN + EARLY only, with or without the column sums (pha_gemm4p_batched has checked)
+template <typename T>
+int launch192(const Args& a, int grid, hipStream_t st) {
+  if (a.epi & EPI_COLSUM) hipLaunchKernelGGL((gemm4p192_kernel<T, true>), dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((gemm4p192_kernel<T, false>), dim3(grid), dim3(256), 0, st, a);
+  return (int)hipGetLastError();
+}
+
 template <typename T, bool BIAS>
 int launch(const Args& a, int ako, int bko, int trans, int grid, hipStream_t st) {
   if (a.epi & EPI_EARLY) return launch_e<T, BIAS, true>(a, ako, bko, trans, grid, st);
@@ -1799,16 +2171,34 @@ PHA_API int pha_gemm4p_batched(int dt, const void* a, const void* b, void* c, lo
                                   !(epi & g4p::EPI_EARLY) || ((epi >> g4p::EPI_KSTAG_SHIFT) & 3) || (epi & g4p::EPI_GELU)))
     return (int)hipErrorInvalidValue;
   if (splits < 1) splits = 1;
+  // tile width (EPI_BN field): 0 = 256 columns; 1 = 192 columns, built for TN + EARLY alone — one
+  // unsplit, unbatched product, no epilogue function but the column sums, no measurement flags (the
+  // schedule-variant fields of the 256 form are accepted and ignored: it has one schedule)
+  const int bn_code = (epi >> g4p::EPI_BN_SHIFT) & 3;
+  if (bn_code > 1) return (int)hipErrorInvalidValue;
+  const bool bn192 = bn_code == 1;
+  if (bn192) {
+    const int allowed = g4p::EPI_EARLY | g4p::EPI_COLSUM | (3 << g4p::EPI_BN_SHIFT) | (15 << g4p::EPI_LATE_SHIFT) |
+                        (3 << g4p::EPI_SPREAD_SHIFT);
+    if (!a_kouter || !b_kouter || trans || splits > 1 || batch != 1 || !(epi & g4p::EPI_EARLY) || (epi & ~allowed))
+      return (int)hipErrorInvalidValue;
+  }
+  const long bn = bn192 ? g4p::N_BN : 256;
   if (batch < 1 || (batch > 1 && (splits > 1 || (epi & g4p::EPI_GELU) || (sa | sb | sc) % 8 || sa < 0 || sb < 0 || sc < 0)))
     return (int)hipErrorInvalidValue;
-  if ((double)batch * ((M + 255) / 256) * ((N + 255) / 256) >= 2147483647.0) return (int)hipErrorInvalidValue;
+  if ((double)batch * ((M + 255) / 256) * ((N + bn - 1) / bn) >= 2147483647.0) return (int)hipErrorInvalidValue;
   if (splits > 1 && (!ws || (K / 64) % splits || !a_kouter || !b_kouter || trans || (size_t)ws & 15))
     return (int)hipErrorInvalidValue;
-  const long tiles = ((M + 255) / 256) * ((N + 255) / 256) * splits * batch;
+  const long tiles = ((M + 255) / 256) * ((N + bn - 1) / bn) * splits * batch;
   if (grid <= 0 || grid > tiles) grid = (int)tiles;
   if (group_m <= 0) group_m = 4;
   g4p::Args p{a, b, c, bias, (int)M, (int)N, (int)K, (int)lda, (int)ldb, (int)ldc, epi, group_m, ws, splits, aux,
               batch, sa, sb, sc};
+  if (bn192) {
+    if (dt == kBF16) return g4p::launch192<bf16_t>(p, grid, stream);
+    if (dt == kF16) return g4p::launch192<half_t>(p, grid, stream);
+    return (int)hipErrorInvalidValue;
+  }
   const bool bs = epi & g4p::EPI_BIAS;
   if (dt == kBF16) return bs ? g4p::launch<bf16_t, true>(p, a_kouter, b_kouter, trans, grid, stream)
                              : g4p::launch<bf16_t, false>(p, a_kouter, b_kouter, trans, grid, stream);

@@ -34,6 +34,8 @@ G4P_GELU_DAUX = 4    # gemm4p NT bias + GELU: aux <- gelu_tanh'(acc + bias) inst
 G4P_MULAUX = 8       # gemm4p NT: C = acc * aux (aux an input shaped like C)
 G4P_COLSUM = 1 << 27  # gemm4p TN + EARLY: column sums of B (bias gradient) from the MFMA B fragments
 G4P_SPREAD_SHIFT = 28  # gemm4p NT + EARLY, bits 28-29: LDS-DMA placement over 24-28 MFMA groups
+G4P_BN_SHIFT = 10      # gemm4p, bits 10-11: tile width (0: 256 columns, 1: 192 columns — TN + EARLY, unsplit)
+_BN_CODE = {256: 0, 192: 1}
 _L = _lib.loaded
 
 
@@ -138,7 +140,7 @@ def _group_m(a_kouter, b_kouter, K, N):
 
 
 def gemm_p(a, b, a_kouter=False, b_kouter=False, bias=None, out=None, trans_out=False, epi_extra=0, grid=0,
-           group_m=0, splits=1, gelu_aux=None, colsum=False, gelu_deriv=False, mul_aux=None):
+           group_m=0, splits=1, gelu_aux=None, colsum=False, gelu_deriv=False, mul_aux=None, bn=256):
     """C = op(A) @ op(B) (+ bias[output column]) on the persistent epilogue-overlapped kernel
     (csrc/kernels/gemm4p.hip). Layouts: NT (False, False), TN (True, True), and with trans_out
     (True, False) the transposed product C^T [N, M] (``nn_p`` runs x @ W through it).
@@ -151,7 +153,9 @@ def gemm_p(a, b, a_kouter=False, b_kouter=False, bias=None, out=None, trans_out=
     input shaped and strided like C (the MLP's fc2 input gradient times the stored GELU derivative).
     colsum (TN only): also the column sums of B over K (a linear layer's bias gradient sum_t dY[t]),
     summed by the main loop from the B fragments it already holds; returns (C, fp32 partials
-    [2 * splits * ceil(M / 256) (+ 8 workspace rows), N]) — finish with colsum_rows_finish."""
+    [2 * splits * ceil(M / 256) (+ 8 workspace rows), N]) — finish with colsum_rows_finish.
+    bn: tile width, 256 or 192 (TN, unsplit, early schedule only: 256 x 192 tiles, ``_tn_bn`` picks it
+    where they fill the CUs' rounds better); the results are bitwise the same either way."""
     assert a.dtype in (torch.bfloat16, torch.float16) and b.dtype == a.dtype and a.dim() == 2 and b.dim() == 2
     assert a.stride(1) == 1 and b.stride(1) == 1
     M, Ka = (a.shape[1], a.shape[0]) if a_kouter else (a.shape[0], a.shape[1])
@@ -161,7 +165,8 @@ def gemm_p(a, b, a_kouter=False, b_kouter=False, bias=None, out=None, trans_out=
     OM, ON = (N, M) if trans_out else (M, N)
     c = out if out is not None else torch.empty(OM, ON, dtype=a.dtype, device=a.device)
     assert c.shape == (OM, ON) and c.stride(1) == 1
-    epi = epi_extra | _epi_default(a_kouter, b_kouter, trans_out, Ka)
+    # (a width the kernel does not know goes down as the reserved code 3: the entry point refuses it)
+    epi = epi_extra | _epi_default(a_kouter, b_kouter, trans_out, Ka) | (_BN_CODE.get(bn, 3) << G4P_BN_SHIFT)
     if bias is not None:
         bias = bias.float().contiguous()
         assert bias.numel() == ON
@@ -427,7 +432,8 @@ def _lib_call(layout, name, shape, fn):
 def _splits(M, N, K, dev):
     """split-K factor for a weight gradient: grids of >= 2 rounds stay unsplit, and so do grids of
     >= 3/4 of a round (the qkv dW's 192 tiles unsplit beat split 4: 714 vs 739 us sustained,
-    profiles/tn_wgrad_r5/tn_sustain.log). Below that, the power of two (<= 16, dividing the K-tiles,
+    profiles/tn_wgrad_r5/tn_sustain.log; its idle quarter of the CUs is filled without slabs or a
+    reduce pass by the 192-column tile instead, ``_tn_bn``). Below that, the power of two (<= 16, dividing the K-tiles,
     >= 4 K-tiles per item) with the least modelled time: rounds of work items x K-tiles per item x
     0.76 us (one K-tile of a 256 x 256 tile) + splits x tiles x 0.12 us (each item's fp32 slab written
     and read back by the in-order reduce). Filling every CU is not the goal: BERT-base's fc1 / fc2
@@ -446,6 +452,34 @@ def _splits(M, N, K, dev):
             best, best_t = sp, t
         sp *= 2
     return best
+
+
+# per-item time of a 256 x 192 tile over 0.75 x a 256 x 256 tile's (its share of the FLOPs), both at a
+# full round of the CUs: the narrower tile re-reads the A panel for 3/4 of the columns (lower
+# arithmetic intensity). Measured on the fc1 dW operands (2048 x 8192, K = 98,304, sustained): 256
+# items of 256 x 192 over 6144 of the columns 1882 us, 256 items of 256 x 256 over all of them 2282 us,
+# 1882 / (0.75 x 2282) = 1.100 (profiles/tn_bn192/parts.txt, tools/tn_bn192.py).
+TN_BN192_PENALTY = 1.10
+
+
+def _tn_bn_model(M, N, cus):
+    """modelled time of an unsplit TN product on both tile widths, in units of one 256 x 256 item:
+    rounds of the work items over the CUs x per-item time -> {256: t, 192: t}"""
+    tm = -(-M // 256)
+    return {256: -(-tm * -(-N // 256) // cus) * 1.0,
+            192: -(-tm * -(-N // 192) // cus) * 0.75 * TN_BN192_PENALTY}
+
+
+def _tn_bn(M, N, splits, cus):
+    """tile width of a TN product, static per shape (the same on every rank): 192 when the product is
+    unsplit, N is a multiple of 192 and the 256 x 192 items fill whole rounds of the CUs with less
+    modelled time than the 256 x 256 ones — GPT-3 1.3B's qkv dW (2048 x 6144 on 256 CUs: 256 items,
+    one full round, instead of 192 with a quarter of the chip idle). PHA_TN_BN=256 keeps the old
+    tile everywhere."""
+    if os.environ.get("PHA_TN_BN", "") == "256" or splits != 1 or N % 192:
+        return 256
+    t = _tn_bn_model(M, N, cus)
+    return 192 if t[192] < t[256] else 256
 
 
 def _pad2(t, rm, cm):
@@ -550,7 +584,8 @@ def mm_tn(a, b):
     if _own_ok("tn", a, b) and b.dtype == a.dtype:
         a, b = _c(a), _c(b)
         if supported(M, N, K, a, b):
-            return gemm_p(a, b, True, True, splits=_splits(M, N, K, a.device))
+            sp = _splits(M, N, K, a.device)
+            return gemm_p(a, b, True, True, splits=sp, bn=_tn_bn(M, N, sp, _num_cus(a.device)))
         if _own_fits(a) and _own_fits(b):
             ap, bp = _pad2(a, 64, 8), _pad2(b, 64, 8)
             return gemm_p(ap, bp, True, True, splits=_splits(ap.shape[1], bp.shape[1], ap.shape[0], a.device))[:M, :N]
@@ -568,7 +603,8 @@ def mm_tn_db(a, b, db_dtype=None):
     if _own_ok("tn", a, b) and b.dtype == a.dtype and os.environ.get("PHA_TN_COLSUM", "1") != "0":
         a, b = _c(a), _c(b)
         if supported(M, N, K, a, b):
-            c, part = gemm_p(a, b, True, True, splits=_splits(M, N, K, a.device), colsum=True)
+            sp = _splits(M, N, K, a.device)
+            c, part = gemm_p(a, b, True, True, splits=sp, colsum=True, bn=_tn_bn(M, N, sp, _num_cus(a.device)))
             return c, colsum_rows_finish(part, db_dtype or b.dtype)
     from . import hip as _hip
     return mm_tn(a, b), _hip.col_sum(b, db_dtype)
