@@ -253,7 +253,173 @@ struct Sched {
     tm = __builtin_amdgcn_readfirstlane(first_m + in % gsize);
     tn = __builtin_amdgcn_readfirstlane(in / gsize);
   }
+  // this workgroup's share of tiles_m x tiles_n x nsplit x batch work items (epi: EPI_ROUNDS alone)
+  __device__ __forceinline__ void init(int tm, int tn, int nsplit, int batch, int group_m, int epi) {
+    tiles_m = tm;
+    tiles_n = tn;
+    splits = nsplit;
+    per_batch = tiles_m * tiles_n;
+    total = per_batch * nsplit * batch;
+    G = gridDim.x;
+    gm = group_m;
+    const int bid = blockIdx.x;
+    const int q8 = G >> 3, r8 = G & 7, xcd = bid & 7;
+    pos = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    if (r8 == 0 && !(epi & EPI_ROUNDS)) {
+      const int qt = total >> 3, rt = total & 7;
+      c0 = (xcd < rt ? xcd * (qt + 1) : rt * (qt + 1) + (xcd - rt) * qt) + (bid >> 3);
+      c1 = c0 - (bid >> 3) + qt + (xcd < rt ? 1 : 0);
+      step = q8;
+    } else {
+      c0 = pos;
+      c1 = total;
+      step = G;
+    }
+  }
 };
+
+// One accumulator tile (4 AGPRs) into VGPRs. As asm: read as plain C++ uses, the register allocator
+// answered the epilogue's reads by splitting every accumulator's live range into VGPR copies at the
+// tile boundary (60-150 spilled VGPRs); opaque, it keeps them in place (0 spills). The last MFMA
+// writing any of these registers is >= 60 MFMAs back (no hazard wait states needed).
+__device__ __forceinline__ void acc_read(const f32x4& x, float (&v)[4]) {
+  asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
+               "v_accvgpr_read_b32 %3, %7"
+               : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]) : "a"(x[0]), "a"(x[1]), "a"(x[2]), "a"(x[3]));
+}
+
+// 8 values -> a lane's 16-B row segment: pack, then lanes of odd 16-lane rows trade their first
+// tile's half for the even rows' second-tile half
+template <typename T>
+__device__ __forceinline__ u32x4v pack_swap(const float (&a)[4], const float (&b)[4]) {
+  unsigned q00 = pk<T>(a[0], a[1]), q01 = pk<T>(a[2], a[3]);
+  unsigned q10 = pk<T>(b[0], b[1]), q11 = pk<T>(b[2], b[3]);
+  const auto s0 = __builtin_amdgcn_permlane16_swap(q00, q10, false, false);
+  const auto s1 = __builtin_amdgcn_permlane16_swap(q01, q11, false, false);
+  return u32x4v{s0[0], s1[0], s0[1], s1[1]};
+}
+
+// A lane's 16-B row segments of the tile being written out: e_base is the wave's first output row
+// at the tile's first column, e_rows / e_cols the valid rows / columns from there; the lane's
+// segment of row block rb and column block cb is row rb * 16 + fr, columns lcol + cb * 16 onwards.
+// Bounds: the buffer's base is the block's first row and its size the rows left, so rows past
+// the output are dropped by the buffer range check; a lane whose columns (multiples of 8,
+// No % 8 == 0) start past the last column gets an offset past any size. Only the lane's
+// column offset is a VGPR; row block and column block go to the scalar base / the immediate offset.
+struct Seg {
+  const char* e_base;
+  int e_rows, e_cols, ldc2, lcol;   // ldc2: output row bytes
+  unsigned lane_voff;               // fr * ldc2 + lcol * (element bytes)
+  // bytes of row block rb inside the output (the descriptor's size), and whether column block cb is
+  // inside it. The pair stores take both first, then their values, then the descriptor: hipcc
+  // schedules the epilogue's address arithmetic among the MFMAs in source order, and this is the
+  // order the kernels were tuned with
+  __device__ __forceinline__ int nbytes(int rb) const {
+    return __builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
+  }
+  // (the guard alone: with the select inside the helper hipcc placed it after the pair swap instead
+  // of in the wait state before it, in every store of every build)
+  __device__ __forceinline__ bool in_cols(int cb) const { return lcol + cb * 16 < e_cols; }
+  static constexpr unsigned OOB = 0x80000000u;   // an offset past any buffer size
+  // descriptor inputs readfirstlane'd: provably uniform, so the descriptor lives in SGPRs
+  // (no per-store waterfall loop, cdna_hip_programming.md T20)
+  __device__ __forceinline__ void* row_ptr(const char* base, int rb) const {
+    const size_t bp = (size_t)(base + (size_t)rb * 16 * ldc2);
+    const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp);
+    const unsigned bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
+    return reinterpret_cast<void*>(((size_t)bhi << 32) | blo);
+  }
+  static __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(void* row, int nbytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(row, (short)0, nbytes, 0x00020000);
+  }
+  __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const char* base, int rb, int nbytes) const {
+    return rsrc(row_ptr(base, rb), nbytes);
+  }
+  // the store itself (off: lane_voff or OOB, + the column block's bytes). Non-temporal by default (the output
+  // is not re-read by this kernel; 3 % faster measured, profiles/gemm4p_store_ab_r3.log)
+  static __device__ __forceinline__ void put(u32x4v q, __amdgpu_buffer_rsrc_t rs, unsigned off, bool temporal = false) {
+    if (temporal) __builtin_amdgcn_raw_buffer_store_b128(q, rs, off, 0, 0);
+    else __builtin_amdgcn_raw_buffer_store_b128(q, rs, off, 0, 2);
+  }
+  // accumulator tiles (x0, x1) of a pair as 16-bit values into segment (rb, cb), no epilogue function
+  template <typename T>
+  __device__ __forceinline__ void store_acc(const f32x4& x0, const f32x4& x1, int rb, int cb, bool temporal = false) const {
+    float v0[4], v1[4];
+    acc_read(x0, v0);
+    acc_read(x1, v1);
+    const int nb = nbytes(rb);
+    const unsigned vo = in_cols(cb) ? lane_voff : OOB;
+    const u32x4v q = pack_swap<T>(v0, v1);
+    put(q, rsrc(e_base, rb, nb), vo + cb * 32, temporal);
+  }
+  // The pair layout of 16-bit outputs: after the pair swap a lane holds 8 consecutive columns starting
+  // at wcol (the wave's first column) + (pair base)*16 + (fk & 1) * 16 + (fk >> 1) * 8 of output row
+  // (row base) + fr. No tile yet: zero rows, every store is dropped.
+  static __device__ __forceinline__ Seg pairs(const void* c, int ldc2, int wcol, int fr, int fk) {
+    const int lcol = wcol + (fk & 1) * 16 + (fk >> 1) * 8;
+    return Seg{static_cast<const char*>(c), 0, 0, ldc2, lcol, (unsigned)(fr * ldc2 + lcol * 2)};
+  }
+  // the tile at output row r0 (the wave's rows from wrow on) and column c0 of the Mo x No 16-bit
+  // outputs at c (nostore, measurement only: zero rows, every store is issued and dropped)
+  __device__ __forceinline__ void set_tile(const char* c, int r0, int wrow, int c0, int Mo, int No, bool nostore = false) {
+    e_base = c + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
+    e_rows = nostore ? 0 : Mo - r0 - wrow;
+    e_cols = No - c0;
+  }
+};
+
+// ---- column sums of B (EPI_COLSUM) for NB B fragments per wave (8: 256-column tiles, 6: 192) ----------
+// The item of round r is summed over its K-tiles [klo, khi) by its tile row (each of the tiles_m
+// tile rows takes its own 1/tiles_m of the K range, so the extra VALU work is spread over the
+// grid); wave row wr takes k-half wr of each of them. The range, the selector and the K-tile loop
+// cut at klo / khi stay in the kernels: computed in helpers, hipcc made other scalar code of the
+// whole K loop (profiles/g4p_shared/).
+//
+// One MFMA group's share (branch-free: a taken branch per group cost 12 % of the TN kernel): the 8
+// k-values of a B fragment dotted with onesel — 1.0 x 2 on the wave row that sums this k-half of
+// this K-tile, 0 on the other
+template <typename T>
+__device__ __forceinline__ void cs_add(float& c, const uint4& f, unsigned onesel) {
+  c = dot2sel<T>(f.x, onesel, c);
+  c = dot2sel<T>(f.y, onesel, c);
+  c = dot2sel<T>(f.z, onesel, c);
+  c = dot2sel<T>(f.w, onesel, c);
+}
+// The item is done: sum the 4 k-quarters (lanes l, l+16, l+32, l+48) of every fragment and clear
+// csum[]. The swaps pair DIFFERENT fragments (a swap of a register with itself is a no-op), on 8
+// slots (NB = 6: fragments 6, 7 are zeros): after permlane32_swap(f_j, f_j+4) + add, lanes 0-31 hold
+// f_j's half sums and lanes 32-63 f_j+4's; after permlane16_swap(u_j, u_j+1) + add, 16-lane row
+// 0..3 holds the totals of fragments (j, j+1, j+4, j+5). Lane row fk then stores two fragments (NB =
+// 6: rows 2, 3 one) to row (slice * tiles_m + tm) * 2 + wr of the fp32 partials [2 * splits * tiles_m][N]
+template <int NB>
+__device__ __forceinline__ void cs_finish(float (&csum)[NB], const Sched& sc, int r, void* aux, int N, int wr, int wc,
+                                          int fr, int fk) {
+  int tm, tn, slice, bi;
+  sc.tile(r, tm, tn, slice, bi);
+  // (asm swaps: hipcc's permlane*_swap builtins fed into an add came out as vdst + vdst, the
+  // second result dropped — the ISA showed v_add_f32 vX, vA, vA after v_permlane32_swap vA, vB)
+  float u[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float x0 = csum[j], x1 = j + 4 < NB ? csum[j + 4] : 0.f;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
+    u[j] = x0 + x1;
+  }
+  float w[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    float x0 = u[2 * j], x1 = u[2 * j + 1];
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
+    w[j] = x0 + x1;
+  }
+#pragma unroll
+  for (int j = 0; j < NB; ++j) csum[j] = 0.f;
+  const int f0 = (fk & 1) + (fk >> 1) * 4;   // w[0]: fragment f0, w[1]: fragment f0 + 2
+  float* row = static_cast<float*>(aux) + (size_t)((slice * sc.tiles_m + tm) * 2 + wr) * N;
+  const int c0 = tn * (NB * 32) + wc * (NB * 16) + 16 * f0 + fr;
+  if (c0 < N) row[c0] = w[0];
+  if ((NB == 8 || fk < 2) && c0 + 32 < N) row[c0 + 32] = w[1];
+}
 
 // SPLIT: the K range of every tile is cut into p.splits slices (separate work items, for problems
 // with fewer tiles than CUs); each item writes its fp32 partial tile to its slab of p.ws and
@@ -274,28 +440,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nk = (K >> 6) / nsplit;   // K-tiles per work item
 
   Sched sc;
-  sc.tiles_m = (M + 255) >> 8;
-  sc.tiles_n = (N + 255) >> 8;
-  sc.splits = nsplit;
-  sc.per_batch = sc.tiles_m * sc.tiles_n;
-  sc.total = sc.per_batch * nsplit * p.batch;
-  sc.G = gridDim.x;
-  sc.gm = p.group_m;
-  {
-    const int bid = blockIdx.x, G = gridDim.x;
-    const int q8 = G >> 3, r8 = G & 7, xcd = bid & 7;
-    sc.pos = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    if (r8 == 0 && !(p.epi & EPI_ROUNDS)) {
-      const int qt = sc.total >> 3, rt = sc.total & 7;
-      sc.c0 = (xcd < rt ? xcd * (qt + 1) : rt * (qt + 1) + (xcd - rt) * qt) + (bid >> 3);
-      sc.c1 = sc.c0 - (bid >> 3) + qt + (xcd < rt ? 1 : 0);
-      sc.step = q8;
-    } else {
-      sc.c0 = sc.pos;
-      sc.c1 = sc.total;
-      sc.step = G;
-    }
-  }
+  sc.init((M + 255) >> 8, (N + 255) >> 8, nsplit, p.batch, p.group_m, p.epi);
   if (!sc.valid(0)) return;
   if (p.epi & EPI_STAGGER) {
     const int n = (blockIdx.x & 7) * ((p.epi >> 16) & 255);
@@ -430,37 +575,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int Mo = OT ? N : M, No = OT ? M : N;
   const int ldc2 = SPLIT ? No * 4 : p.ldc * 2;   // output row bytes (split-K: the fp32 slab)
   const int wrow = (OT ? wc : wr) * 128;                                  // wave's first output row
-  const int lcol = (OT ? wr : wc) * 128 + (fk & 1) * 16 + (fk >> 1) * 8;   // + pair base * 16
-  const unsigned lane_voff = (unsigned)(fr * ldc2 + lcol * 2);
   // split-K (non-OT only): a lane's 4 fp32 of tile j sit at columns wc*128 + j*16 + 4fk
   const int lcol4 = wc * 128 + 4 * fk;
-  const unsigned lane_voff4 = (unsigned)(fr * ldc2 + lcol4 * 4);
-  // the tile being written out: output origin (bytes), valid rows / columns from the wave's origin,
-  // bias slot
-  const char* e_base = static_cast<const char*>(p.c);
+  // the tile being written out (seg), its aux origin and its bias slot
+  Seg seg = SPLIT ? Seg{static_cast<const char*>(p.c), 0, 0, ldc2, lcol4, (unsigned)(fr * ldc2 + lcol4 * 4)}
+                  : Seg::pairs(p.c, ldc2, (OT ? wr : wc) * 128, fr, fk);
   const char* e_aux = static_cast<const char*>(p.aux);
-  int e_rows = 0, e_cols = 0, e_slot = 0;
+  int e_slot = 0;
   auto set_epi = [&](int r) {
     int tm, tn, slice, bi;
     sc.tile(r, tm, tn, slice, bi);
     const int r0 = OT ? tn << 8 : tm << 8, c0 = OT ? tm << 8 : tn << 8;
     e_slot = r & 3;
     if constexpr (SPLIT)
-      e_base = reinterpret_cast<const char*>(p.ws) + (size_t)slice * Mo * No * 4 +
-               ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 4);
+      seg.e_base = reinterpret_cast<const char*>(p.ws) + (size_t)slice * Mo * No * 4 +
+                   ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 4);
     else
-      e_base = static_cast<const char*>(p.c) + (size_t)bi * p.sc * 2 + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
+      seg.e_base = static_cast<const char*>(p.c) + (size_t)bi * p.sc * 2 + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
     if constexpr (GELU || MUL) e_aux = static_cast<const char*>(p.aux) + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
     // (EPI_NOSTORE, measurement only: zero rows, every store is issued and dropped)
-    e_rows = (p.epi & EPI_NOSTORE) ? 0 : Mo - r0 - wrow;
-    e_cols = No - c0;
+    seg.e_rows = (p.epi & EPI_NOSTORE) ? 0 : Mo - r0 - wrow;
+    seg.e_cols = No - c0;
   };
-  // pair (t0, t0 + 1) of the wave's output-row block rb: one 16-B store of the lane's 8 columns.
-  // Bounds: the buffer's base is the block's first row and its size the rows left, so rows past
-  // the output are dropped by the buffer range check; a lane whose 8 columns (multiples of 8,
-  // No % 8 == 0) start past the last column gets an offset past any size. Only the lane's
-  // column offset is a VGPR; row block and pair go to the scalar base / the immediate offset.
-  //
   // MUL: the lane's aux segments in flight, a ring of 2 * MW loads of 16 B (see mul_younger). Load li
   // (0..31) of a tile belongs to pair li & 1 of MFMA group li >> 1 and reads exactly the 16 B that
   // store_pair writes for that pair, through the same bounds (rows past the output and column
@@ -473,13 +609,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   u32x4v aw[MUL ? 2 * MW : 2];
   auto aux_load = [&](int li) {
     const int g = li >> 1, rb = g >> 1, cb = (g & 1) * 4 + (li & 1) * 2;
+    // (Seg::rsrc's descriptor as the four words the asm operand takes)
     const size_t bp = (size_t)(e_aux + (size_t)rb * 16 * ldc2);
     u32x4v rs;
     rs[0] = __builtin_amdgcn_readfirstlane((unsigned)bp);
     rs[1] = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32)) & 0xffffu;
-    rs[2] = (unsigned)__builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
+    rs[2] = (unsigned)seg.nbytes(rb);
     rs[3] = 0x00020000u;
-    const unsigned voff = (lcol + cb * 16 < e_cols) ? lane_voff : 0x80000000u;
+    const unsigned voff = (seg.in_cols(cb) ? seg.lane_voff : Seg::OOB);
     asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3"
                  : "=v"(aw[MUL ? li % (2 * MW) : 0]) : "v"(voff), "s"(rs), "i"(cb * 32) : "memory");
   };
@@ -499,39 +636,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int li = 0; li < 2 * MW; ++li) aux_load(li);
   };
+  // pair (t0, t0 + 1) of the wave's output-row block rb: one 16-B store of the lane's 8 columns
   auto store_pair = [&](const f32x4& x0, const f32x4& x1, int rb, int cb, int li = 0) {
-    // AGPR -> VGPR reads as asm: as plain C++ uses, the register allocator answered the
-    // epilogue's reads by splitting every accumulator's live range into VGPR copies at the tile
-    // boundary (60-150 spilled VGPRs); opaque, it keeps them in place (0 spills). The last MFMA
-    // writing any of these registers is >= 60 MFMAs back (no hazard wait states needed).
     float v0[4], v1[4];
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v0[0]), "=v"(v0[1]), "=v"(v0[2]), "=v"(v0[3]) : "a"(x0[0]), "a"(x0[1]), "a"(x0[2]), "a"(x0[3]));
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v1[0]), "=v"(v1[1]), "=v"(v1[2]), "=v"(v1[3]) : "a"(x1[0]), "a"(x1[1]), "a"(x1[2]), "a"(x1[3]));
-    const int nbytes = __builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
-    const unsigned voff = (lcol + cb * 16 < e_cols) ? lane_voff : 0x80000000u;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    // 8 values -> the lane's 16-B row segment: pack, then lanes of odd 16-lane rows trade their
-    // tile-t0 half for the even rows' tile-(t0+1) half
-    auto pack_swap = [&](const float (&a)[4], const float (&b)[4]) {
-      unsigned q00 = pk<T>(a[0], a[1]), q01 = pk<T>(a[2], a[3]);
-      unsigned q10 = pk<T>(b[0], b[1]), q11 = pk<T>(b[2], b[3]);
-      const auto s0 = __builtin_amdgcn_permlane16_swap(q00, q10, false, false);
-      const auto s1 = __builtin_amdgcn_permlane16_swap(q01, q11, false, false);
-      return u32x4{s0[0], s1[0], s0[1], s1[1]};
-    };
-    // descriptor inputs readfirstlane'd: provably uniform, so the descriptor lives in SGPRs
-    // (no per-store waterfall loop, cdna_hip_programming.md T20)
-    auto rsrc = [&](const char* base) {
-      const size_t bp = (size_t)(base + (size_t)rb * 16 * ldc2);
-      const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp);
-      const unsigned bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-      return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((size_t)bhi << 32) | blo), (short)0, nbytes,
-                                               0x00020000);
-    };
+    acc_read(x0, v0);
+    acc_read(x1, v1);
+    const int nbytes = seg.nbytes(rb);
+    const unsigned voff = (seg.in_cols(cb) ? seg.lane_voff : Seg::OOB);
     if constexpr (MUL) {
       // the lane's aux segment back to the accumulator layout: the inverse of pack_swap (the swap is
       // its own inverse), unpacked to fp32, times the fp32 accumulators
@@ -550,7 +661,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
     }
     if constexpr (GELU && !DAUX)   // the pre-activation (before the bias) for the backward pass
-      __builtin_amdgcn_raw_buffer_store_b128(pack_swap(v0, v1), rsrc(e_aux), voff + cb * 32, 0, 2);
+      Seg::put(pack_swap<T>(v0, v1), seg.rsrc(e_aux, rb, nbytes), voff + cb * 32);
     if constexpr (BIAS) {   // bias of the lane's pre-swap columns cb*16 + 4fk .. +3 and (cb+1)*16 + ...
       const unsigned char* bs = smem + BIAS_OFF + e_slot * 1024 + (OT ? wr : wc) * 512 + 16 * fk;
       const f32x4 b0 = *reinterpret_cast<const f32x4*>(bs + cb * 64);
@@ -584,7 +695,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       const auto s0 = __builtin_amdgcn_permlane16_swap(qd[0], qd[2], false, false);
       const auto s1 = __builtin_amdgcn_permlane16_swap(qd[1], qd[3], false, false);
-      __builtin_amdgcn_raw_buffer_store_b128(u32x4{s0[0], s1[0], s0[1], s1[1]}, rsrc(e_aux), voff + cb * 32, 0, 2);
+      Seg::put(u32x4v{s0[0], s1[0], s0[1], s1[1]}, seg.rsrc(e_aux, rb, nbytes), voff + cb * 32);
     } else if constexpr (GELU) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -592,29 +703,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         v1[e] = gelu_t(v1[e]);
       }
     }
-    const auto rs = rsrc(e_base);
-    const u32x4 q = pack_swap(v0, v1);
-    // non-temporal by default (the output is not re-read by this kernel; 3 % faster measured,
-    // profiles/gemm4p_store_ab_r3.log)
-    if (p.epi & EPI_TEMPORAL) __builtin_amdgcn_raw_buffer_store_b128(q, rs, voff + cb * 32, 0, 0);
-    else __builtin_amdgcn_raw_buffer_store_b128(q, rs, voff + cb * 32, 0, 2);
+    const __amdgpu_buffer_rsrc_t rs = seg.rsrc(seg.e_base, rb, nbytes);
+    const u32x4v q = pack_swap<T>(v0, v1);
+    Seg::put(q, rs, voff + cb * 32, p.epi & EPI_TEMPORAL);
   };
 
   // split-K: acc tile (rb, cb) of the wave as fp32, one 16-B store per lane
   auto store_f32 = [&](const f32x4& x, int rb, int cb) {
     float v[4];
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]) : "a"(x[0]), "a"(x[1]), "a"(x[2]), "a"(x[3]));
-    const size_t bp = (size_t)(e_base + (size_t)rb * 16 * ldc2);
-    const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp);
-    const unsigned bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-    const int nbytes = __builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<void*>(((size_t)bhi << 32) | blo), (short)0, nbytes, 0x00020000);
-    const unsigned voff = (lcol4 + cb * 16 < e_cols) ? lane_voff4 : 0x80000000u;
+    acc_read(x, v);
     typedef float f4 __attribute__((ext_vector_type(4)));
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, f4{v[0], v[1], v[2], v[3]}), rs, voff + cb * 64, 0, 2);
+    void* row = seg.row_ptr(seg.e_base, rb);   // (this store's order: the row pointer before the size)
+    const __amdgpu_buffer_rsrc_t rs = Seg::rsrc(row, seg.nbytes(rb));
+    Seg::put(__builtin_bit_cast(u32x4v, f4{v[0], v[1], v[2], v[3]}), rs, (seg.in_cols(cb) ? seg.lane_voff : Seg::OOB) + cb * 64);
   };
 
   f32x4 acc[8][8];
@@ -848,16 +949,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           else mma0<T>(acc[i][j], cb[j], ca[i]);
         }
       }
-      // CS phases (branch-free: a taken branch per group cost 12 % of the TN kernel): group s < 8
-      // adds the 8 k-values of B fragment s (column wc*128 + 16s + fr) dotted with onesel — 1.0 x 2
-      // on the wave row that sums this k-half of this K-tile, 0 on the other
+      // CS phases: group s < 8 sums B fragment s (column wc*128 + 16s + fr)
       if constexpr (decltype(cs_c)::value) {
-        if (s < 8) {   // (s is a constant after unrolling: no branch)
-          csum[s & 7] = dot2sel<T>(cb[s & 7].x, onesel, csum[s & 7]);
-          csum[s & 7] = dot2sel<T>(cb[s & 7].y, onesel, csum[s & 7]);
-          csum[s & 7] = dot2sel<T>(cb[s & 7].z, onesel, csum[s & 7]);
-          csum[s & 7] = dot2sel<T>(cb[s & 7].w, onesel, csum[s & 7]);
-        }
+        if (s < 8) cs_add<T>(csum[s & 7], cb[s & 7], onesel);   // (s is a constant after unrolling: no branch)
       } else {
         (void)onesel;
       }
@@ -917,9 +1011,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     using VW2 = std::integral_constant<int, LWG ? VL2 : 0>;
     const unsigned long long sp_0 = STAMP ? __builtin_amdgcn_s_memtime() : 0;
     for (int r = 0; sc.valid(r); ++r) {
-      // CS: the item's K-tiles [klo, khi) are summed by this tile row (each of the tiles_m tile rows
-      // takes its own 1/tiles_m of the K range, so the extra VALU work is spread over the grid);
-      // wave row wr takes k-half wr of each of them
       int klo = 0, khi = 0;
       if constexpr (CS) {
         int tm, tn, slice, bi;
@@ -927,11 +1018,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         klo = __builtin_amdgcn_readfirstlane(tm * nk / sc.tiles_m);
         khi = __builtin_amdgcn_readfirstlane((tm + 1) * nk / sc.tiles_m);
       }
-      // CS: K-tile k's k-half h is summed by wave row h when klo <= k < khi (sel below)
       using CSY = std::integral_constant<bool, CS>;
-      auto sel = [&](int k, int h) -> unsigned {
-        return (CS && k >= klo && k < khi && wr == h) ? ONES2<T> : 0u;
-      };
+      auto sel = [&](int k, int h) -> unsigned { return (CS && k >= klo && k < khi && wr == h) ? ONES2<T> : 0u; };
       {
         const int buf = s & 1;
         phaseE(M2{}, yes{}, VW2{}, fa0, fb0, fa1, fb1, buf, 1, buf, CSY{}, sel(0, 0));
@@ -970,49 +1058,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         stage_end();
       };
       // the K-tile loop cut at klo / khi: only the phases of [klo, khi) carry the dot2s (all-on
-      // dot2 phases cost the TN kernel 9-13 %, profiles/tn_colsum_r6/)
+      // dot2 phases cost the TN kernel 9-13 %, profiles/tn_colsum_r6/). The loop stays in the kernel:
+      // run from a shared helper that calls ktile back, every early build's K loop compiled to other
+      // scalar code (profiles/g4p_shared/)
       if constexpr (CS && PHA_G4P_CS_SPLITLOOP) {
-        using CSN = std::false_type;
         int k = 1;
-        for (; k < klo; ++k, ++s) ktile(CSN{}, k);
-        for (; k < khi; ++k, ++s) ktile(CSY{}, k);
-        for (; k < nk; ++k, ++s) ktile(CSN{}, k);
+        for (; k < klo; ++k, ++s) ktile(no{}, k);
+        for (; k < khi; ++k, ++s) ktile(yes{}, k);
+        for (; k < nk; ++k, ++s) ktile(no{}, k);
       } else {
         for (int k = 1; k < nk; ++k, ++s) ktile(CSY{}, k);
       }
-      if constexpr (CS) {
-        // the item is done: sum the 4 k-quarters (lanes l, l+16, l+32, l+48) of every fragment. The
-        // swaps pair DIFFERENT fragments (a swap of a register with itself is a no-op): after
-        // permlane32_swap(f_j, f_j+4) + add, lanes 0-31 hold f_j's half sums and lanes 32-63 f_j+4's;
-        // after permlane16_swap(u_j, u_j+1) + add, 16-lane row 0..3 holds the totals of fragments
-        // (j, j+1, j+4, j+5). Lane row fk then stores two fragments to row
-        // (slice * tiles_m + tm) * 2 + wr of the fp32 partials [2 * splits * tiles_m][N]
-        int tm, tn, slice, bi;
-        sc.tile(r, tm, tn, slice, bi);
-        // (asm swaps: hipcc's permlane*_swap builtins fed into an add came out as vdst + vdst, the
-        // second result dropped — the ISA showed v_add_f32 vX, vA, vA after v_permlane32_swap vA, vB)
-        float u[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float x0 = csum[j], x1 = csum[j + 4];
-          asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
-          u[j] = x0 + x1;
-        }
-        float w[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          float x0 = u[2 * j], x1 = u[2 * j + 1];
-          asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
-          w[j] = x0 + x1;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) csum[j] = 0.f;
-        const int f0 = (fk & 1) + (fk >> 1) * 4;   // w[0]: fragment f0, w[1]: fragment f0 + 2
-        float* row = static_cast<float*>(p.aux) + (size_t)((slice * sc.tiles_m + tm) * 2 + wr) * N;
-        const int c0 = (tn << 8) + wc * 128 + 16 * f0 + fr;
-        if (c0 < N) row[c0] = w[0];
-        if (c0 + 32 < N) row[c0 + 32] = w[1];
-      }
+      if constexpr (CS) cs_finish(csum, sc, r, p.aux, N, wr, wc, fr, fk);
     }
     if constexpr (STAMP) {   // diagnostic output (vector stores from lane 0 into the workspace)
       const unsigned long long tot = __builtin_amdgcn_s_memtime() - sp_0;
@@ -1150,28 +1207,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nst = K >> 5;   // stages per tile (even, >= 4: the launcher checks)
 
   Sched sc;
-  sc.tiles_m = (M + 255) >> 8;
-  sc.tiles_n = (N + 255) >> 8;
-  sc.splits = 1;
-  sc.per_batch = sc.tiles_m * sc.tiles_n;
-  sc.total = sc.per_batch * p.batch;
-  sc.G = gridDim.x;
-  sc.gm = p.group_m;
-  {
-    const int bid = blockIdx.x, G = gridDim.x;
-    const int q8 = G >> 3, r8 = G & 7, xcd = bid & 7;
-    sc.pos = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    if (r8 == 0 && !(p.epi & EPI_ROUNDS)) {
-      const int qt = sc.total >> 3, rt = sc.total & 7;
-      sc.c0 = (xcd < rt ? xcd * (qt + 1) : rt * (qt + 1) + (xcd - rt) * qt) + (bid >> 3);
-      sc.c1 = sc.c0 - (bid >> 3) + qt + (xcd < rt ? 1 : 0);
-      sc.step = q8;
-    } else {
-      sc.c0 = sc.pos;
-      sc.c1 = sc.total;
-      sc.step = G;
-    }
-  }
+  sc.init((M + 255) >> 8, (N + 255) >> 8, 1, p.batch, p.group_m, p.epi);
   if (!sc.valid(0)) return;
 
   // ---- DMA cursor: round rs, stage ks; 4 A + 4 B pieces (16 rows x 64 B) per wave and stage ----
@@ -1236,47 +1272,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // ---- epilogue geometry (gemm4p's non-OT layout) ------------------------------------------------
   const int ldc2 = p.ldc * 2;
   const int wrow = wr * 128;
-  const int lcol = wc * 128 + (fk & 1) * 16 + (fk >> 1) * 8;
-  const unsigned lane_voff = (unsigned)(fr * ldc2 + lcol * 2);
-  const char* e_base = static_cast<const char*>(p.c);
+  Seg seg = Seg::pairs(p.c, ldc2, wc * 128, fr, fk);
   const char* e_aux = static_cast<const char*>(p.aux);
-  int e_rows = 0, e_cols = 0, e_slot = 0;
+  int e_slot = 0;
   auto set_epi = [&](int r) {
     int tm, tn, slice, bi;
     sc.tile(r, tm, tn, slice, bi);
     const int r0 = tm << 8, c0 = tn << 8;
     e_slot = r & 3;
-    e_base = static_cast<const char*>(p.c) + (size_t)bi * p.sc * 2 + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
+    seg.set_tile(static_cast<const char*>(p.c) + (size_t)bi * p.sc * 2, r0, wrow, c0, M, N, p.epi & EPI_NOSTORE);
     if constexpr (GELU) e_aux = static_cast<const char*>(p.aux) + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
-    e_rows = (p.epi & EPI_NOSTORE) ? 0 : M - r0 - wrow;
-    e_cols = N - c0;
   };
   auto store_pair = [&](const f32x4& x0, const f32x4& x1, int rb, int cb) {
     float v0[4], v1[4];
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v0[0]), "=v"(v0[1]), "=v"(v0[2]), "=v"(v0[3]) : "a"(x0[0]), "a"(x0[1]), "a"(x0[2]), "a"(x0[3]));
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v1[0]), "=v"(v1[1]), "=v"(v1[2]), "=v"(v1[3]) : "a"(x1[0]), "a"(x1[1]), "a"(x1[2]), "a"(x1[3]));
-    const int nbytes = __builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
-    const unsigned voff = (lcol + cb * 16 < e_cols) ? lane_voff : 0x80000000u;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    auto pack_swap = [&](const float (&a)[4], const float (&b)[4]) {
-      unsigned q00 = pk<T>(a[0], a[1]), q01 = pk<T>(a[2], a[3]);
-      unsigned q10 = pk<T>(b[0], b[1]), q11 = pk<T>(b[2], b[3]);
-      const auto s0 = __builtin_amdgcn_permlane16_swap(q00, q10, false, false);
-      const auto s1 = __builtin_amdgcn_permlane16_swap(q01, q11, false, false);
-      return u32x4{s0[0], s1[0], s0[1], s1[1]};
-    };
-    auto rsrc = [&](const char* base) {
-      const size_t bp = (size_t)(base + (size_t)rb * 16 * ldc2);
-      const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp);
-      const unsigned bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-      return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((size_t)bhi << 32) | blo), (short)0, nbytes,
-                                               0x00020000);
-    };
-    if constexpr (GELU) __builtin_amdgcn_raw_buffer_store_b128(pack_swap(v0, v1), rsrc(e_aux), voff + cb * 32, 0, 2);
+    acc_read(x0, v0);
+    acc_read(x1, v1);
+    const int nbytes = seg.nbytes(rb);
+    const unsigned voff = (seg.in_cols(cb) ? seg.lane_voff : Seg::OOB);
+    if constexpr (GELU) Seg::put(pack_swap<T>(v0, v1), seg.rsrc(e_aux, rb, nbytes), voff + cb * 32);
     if constexpr (BIAS) {
       const unsigned char* bs = smem + R_BIAS_OFF + e_slot * 1024 + wc * 512 + 16 * fk;
       const f32x4 b0 = *reinterpret_cast<const f32x4*>(bs + cb * 64);
@@ -1294,10 +1307,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         v1[e] = gelu_t(v1[e]);
       }
     }
-    const auto rs_ = rsrc(e_base);
-    const u32x4 q = pack_swap(v0, v1);
-    if (p.epi & EPI_TEMPORAL) __builtin_amdgcn_raw_buffer_store_b128(q, rs_, voff + cb * 32, 0, 0);
-    else __builtin_amdgcn_raw_buffer_store_b128(q, rs_, voff + cb * 32, 0, 2);
+    const __amdgpu_buffer_rsrc_t rs_ = seg.rsrc(seg.e_base, rb, nbytes);
+    const u32x4v q = pack_swap<T>(v0, v1);
+    Seg::put(q, rs_, voff + cb * 32, p.epi & EPI_TEMPORAL);
   };
 
   f32x4 acc[8][8];
@@ -1413,28 +1425,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nk = K >> 6;   // >= 4 (launcher)
 
   Sched sc;
-  sc.tiles_m = (M + 255) >> 8;
-  sc.tiles_n = (N + 255) >> 8;
-  sc.splits = 1;
-  sc.per_batch = sc.tiles_m * sc.tiles_n;
-  sc.total = sc.per_batch * p.batch;
-  sc.G = gridDim.x;
-  sc.gm = p.group_m;
-  {
-    const int bid = blockIdx.x, G = gridDim.x;
-    const int q8 = G >> 3, r8 = G & 7, xcd = bid & 7;
-    sc.pos = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    if (r8 == 0 && !(p.epi & EPI_ROUNDS)) {
-      const int qt = sc.total >> 3, rt = sc.total & 7;
-      sc.c0 = (xcd < rt ? xcd * (qt + 1) : rt * (qt + 1) + (xcd - rt) * qt) + (bid >> 3);
-      sc.c1 = sc.c0 - (bid >> 3) + qt + (xcd < rt ? 1 : 0);
-      sc.step = q8;
-    } else {
-      sc.c0 = sc.pos;
-      sc.c1 = sc.total;
-      sc.step = G;
-    }
-  }
+  sc.init((M + 255) >> 8, (N + 255) >> 8, 1, p.batch, p.group_m, p.epi);
   if (!sc.valid(0)) return;
 
   const unsigned lds0 = lds_u32(smem);
@@ -1490,43 +1481,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     return *reinterpret_cast<const uint4*>(smem + AD_B0 + slot * AD_SLOT + row * 128 + (((kh * 4 + fk) ^ (fr & 7)) << 4));
   };
 
-  const int ldc2 = p.ldc * 2;
   const int wrow = wr * 128;
-  const int lcol = wc * 128 + (fk & 1) * 16 + (fk >> 1) * 8;
-  const unsigned lane_voff = (unsigned)(fr * ldc2 + lcol * 2);
-  const char* e_base = static_cast<const char*>(p.c);
-  int e_rows = 0, e_cols = 0;
+  Seg seg = Seg::pairs(p.c, p.ldc * 2, wc * 128, fr, fk);
   auto set_epi = [&](int r) {
     int tm, tn, slice, bi;
     sc.tile(r, tm, tn, slice, bi);
-    const int r0 = tm << 8, c0 = tn << 8;
-    e_base = static_cast<const char*>(p.c) + (size_t)bi * p.sc * 2 + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
-    e_rows = (p.epi & EPI_NOSTORE) ? 0 : M - r0 - wrow;
-    e_cols = N - c0;
+    seg.set_tile(static_cast<const char*>(p.c) + (size_t)bi * p.sc * 2, tm << 8, wrow, tn << 8, M, N, p.epi & EPI_NOSTORE);
   };
   auto store_pair = [&](const f32x4& x0, const f32x4& x1, int rb, int cb) {
-    float v0[4], v1[4];
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v0[0]), "=v"(v0[1]), "=v"(v0[2]), "=v"(v0[3]) : "a"(x0[0]), "a"(x0[1]), "a"(x0[2]), "a"(x0[3]));
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v1[0]), "=v"(v1[1]), "=v"(v1[2]), "=v"(v1[3]) : "a"(x1[0]), "a"(x1[1]), "a"(x1[2]), "a"(x1[3]));
-    const int nbytes = __builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
-    const unsigned voff = (lcol + cb * 16 < e_cols) ? lane_voff : 0x80000000u;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    unsigned q00 = pk<T>(v0[0], v0[1]), q01 = pk<T>(v0[2], v0[3]);
-    unsigned q10 = pk<T>(v1[0], v1[1]), q11 = pk<T>(v1[2], v1[3]);
-    const auto s0 = __builtin_amdgcn_permlane16_swap(q00, q10, false, false);
-    const auto s1 = __builtin_amdgcn_permlane16_swap(q01, q11, false, false);
-    const size_t bp = (size_t)(e_base + (size_t)rb * 16 * ldc2);
-    const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp);
-    const unsigned bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-    const auto rsc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((size_t)bhi << 32) | blo), (short)0,
-                                                       nbytes, 0x00020000);
-    const u32x4 qv{s0[0], s1[0], s0[1], s1[1]};
-    if (p.epi & EPI_TEMPORAL) __builtin_amdgcn_raw_buffer_store_b128(qv, rsc, voff + cb * 32, 0, 0);
-    else __builtin_amdgcn_raw_buffer_store_b128(qv, rsc, voff + cb * 32, 0, 2);
+    seg.template store_acc<T>(x0, x1, rb, cb, p.epi & EPI_TEMPORAL);
   };
 
   f32x4 acc[8][8];
@@ -1704,28 +1667,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nk = p.K >> 6;
 
   Sched sc;
-  sc.tiles_m = (M + 255) >> 8;
-  sc.tiles_n = (N + N_BN - 1) / N_BN;
-  sc.splits = 1;
-  sc.per_batch = sc.tiles_m * sc.tiles_n;
-  sc.total = sc.per_batch;
-  sc.G = gridDim.x;
-  sc.gm = p.group_m;
-  {
-    const int bid = blockIdx.x, G = gridDim.x;
-    const int q8 = G >> 3, r8 = G & 7, xcd = bid & 7;
-    sc.pos = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    if (r8 == 0) {
-      const int qt = sc.total >> 3, rt = sc.total & 7;
-      sc.c0 = (xcd < rt ? xcd * (qt + 1) : rt * (qt + 1) + (xcd - rt) * qt) + (bid >> 3);
-      sc.c1 = sc.c0 - (bid >> 3) + qt + (xcd < rt ? 1 : 0);
-      sc.step = q8;
-    } else {
-      sc.c0 = sc.pos;
-      sc.c1 = sc.total;
-      sc.step = G;
-    }
-  }
+  sc.init((M + 255) >> 8, (N + N_BN - 1) / N_BN, 1, 1, p.group_m, 0);
   if (!sc.valid(0)) return;
 
   // ---- staging cursor (round rs, k-tile ks): per-lane DMA offsets of the cursor's tile ------------
@@ -1804,47 +1746,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     else na[r - 6] = readA(rbuf, rkh, r - 6);
   };
 
-  // ---- epilogue geometry: after the pair swap a lane holds 8 consecutive output columns starting
-  // at wc*96 + (pair base)*16 + (fk & 1)*16 + (fk >> 1)*8 of output row wr*128 + (row block)*16 + fr
-  const int ldc2 = p.ldc * 2;
+  // ---- epilogue geometry: the wave's 128 x 96 at (wr*128, wc*96) ------------------------------------
   const int wrow = wr * 128;
-  const int lcol = wc * 96 + (fk & 1) * 16 + (fk >> 1) * 8;
-  const unsigned lane_voff = (unsigned)(fr * ldc2 + lcol * 2);
-  const char* e_base = static_cast<const char*>(p.c);
-  int e_rows = 0, e_cols = 0;   // (no previous tile yet: zero rows, the first epilogue phase's stores are dropped)
+  Seg seg = Seg::pairs(p.c, p.ldc * 2, wc * 96, fr, fk);
   auto set_epi = [&](int r) {
     int tm, tn, slice, bi;
     sc.tile(r, tm, tn, slice, bi);
-    const int r0 = tm << 8, c0 = tn * N_BN;
-    e_base = static_cast<const char*>(p.c) + ((size_t)(r0 + wrow) * ldc2 + (size_t)c0 * 2);
-    e_rows = M - r0 - wrow;
-    e_cols = N - c0;
-  };
-  // pair (cb, cb + 1) of row block rb: gemm4p_kernel's store_pair without an epilogue function (rows
-  // past the output dropped by the buffer's size, column groups past N by an offset past any size)
-  auto store_pair = [&](const f32x4& x0, const f32x4& x1, int rb, int cb) {
-    float v0[4], v1[4];
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v0[0]), "=v"(v0[1]), "=v"(v0[2]), "=v"(v0[3]) : "a"(x0[0]), "a"(x0[1]), "a"(x0[2]), "a"(x0[3]));
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\t"
-                 "v_accvgpr_read_b32 %3, %7"
-                 : "=v"(v1[0]), "=v"(v1[1]), "=v"(v1[2]), "=v"(v1[3]) : "a"(x1[0]), "a"(x1[1]), "a"(x1[2]), "a"(x1[3]));
-    const int nbytes = __builtin_amdgcn_readfirstlane(max(min(e_rows - rb * 16, 16), 0) * ldc2);
-    const unsigned voff = (lcol + cb * 16 < e_cols) ? lane_voff : 0x80000000u;
-    const unsigned q00 = pk<T>(v0[0], v0[1]), q01 = pk<T>(v0[2], v0[3]);
-    const unsigned q10 = pk<T>(v1[0], v1[1]), q11 = pk<T>(v1[2], v1[3]);
-    const auto s0 = __builtin_amdgcn_permlane16_swap(q00, q10, false, false);
-    const auto s1 = __builtin_amdgcn_permlane16_swap(q01, q11, false, false);
-    const size_t bp = (size_t)(e_base + (size_t)rb * 16 * ldc2);
-    const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp);
-    const unsigned bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<void*>(((size_t)bhi << 32) | blo), (short)0, nbytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4v{s0[0], s1[0], s0[1], s1[1]}, rsrc, voff + cb * 32, 0, 2);
+    seg.set_tile(static_cast<const char*>(p.c), tm << 8, wrow, tn * N_BN, M, N);
   };
   auto store_nth = [&](f32x4 (&acc)[8][6], int pr) {   // pair pr (0..23) of the tile
-    store_pair(acc[pr / 3][(pr % 3) * 2], acc[pr / 3][(pr % 3) * 2 + 1], pr / 3, (pr % 3) * 2);
+    seg.template store_acc<T>(acc[pr / 3][(pr % 3) * 2], acc[pr / 3][(pr % 3) * 2 + 1], pr / 3, (pr % 3) * 2);
   };
 
   f32x4 acc[8][6];
@@ -1891,15 +1802,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if constexpr (MODE == 0) acc[i][j] = Mf<T>::mma(cb[j], ca[i], acc[i][j]);
         else mma0<T>(acc[i][j], cb[j], ca[i]);
       }
-      // CS (branch-free, as gemm4p_kernel's): group s < 6 adds the 8 k-values of B fragment s dotted with
-      // onesel — 1.0 x 2 on the wave row that sums this k-half of this K-tile, 0 on the other
+      // CS: group s < 6 sums B fragment s
       if constexpr (decltype(cs_c)::value) {
-        if (s < 6) {
-          csum[s % 6] = dot2sel<T>(cb[s % 6].x, onesel, csum[s % 6]);
-          csum[s % 6] = dot2sel<T>(cb[s % 6].y, onesel, csum[s % 6]);
-          csum[s % 6] = dot2sel<T>(cb[s % 6].z, onesel, csum[s % 6]);
-          csum[s % 6] = dot2sel<T>(cb[s % 6].w, onesel, csum[s % 6]);
-        }
+        if (s < 6) cs_add<T>(csum[s % 6], cb[s % 6], onesel);
       } else {
         (void)onesel;
       }
@@ -1935,8 +1840,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   using CSY = std::integral_constant<bool, CS>;
   int s = 0;   // global K-tile step; buffer s & 1
   for (int r = 0; sc.valid(r); ++r) {
-    // CS: tile row tm sums the item's K-tiles [klo, khi) (its 1/tiles_m of the K range), wave row wr
-    // k-half wr of each — the same ranges and lanes as on the 256 form
     int klo = 0, khi = 0;
     if constexpr (CS) {
       int tm, tn, slice, bi;
@@ -1965,7 +1868,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       phase(M0{}, no{}, cs_c, fa1, fb1, fa0, fb0, buf ^ 1, 0, buf, sel(k, 1));
       stage_end();
     };
-    if constexpr (CS) {   // the K-tile loop cut at klo / khi: only [klo, khi) carries the dot2s
+    if constexpr (CS) {   // the K-tile loop cut at klo / khi, in the kernel for the same reason as gemm4p_kernel's
       int k = 1;
       for (; k < klo; ++k, ++s) ktile(no{}, k);
       for (; k < khi; ++k, ++s) ktile(yes{}, k);
@@ -1973,35 +1876,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     } else {
       for (int k = 1; k < nk; ++k, ++s) ktile(no{}, k);
     }
-    if constexpr (CS) {
-      // the item is done: sum the 4 k-quarters (lanes l, l+16, l+32, l+48) of every fragment with
-      // gemm4p_kernel's swaps on 8 slots, the last two zero: permlane32_swap(f_j, f_j+4) + add, then
-      // permlane16_swap(u_j, u_j+1) + add leave lane row fk with the totals of fragments
-      // f0 = (fk & 1) + (fk >> 1) * 4 and f0 + 2 (fragments 6, 7 do not exist: rows 2, 3 store one)
-      int tm, tn, slice, bi;
-      sc.tile(r, tm, tn, slice, bi);
-      float u[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float x0 = csum[j], x1 = j + 4 < 6 ? csum[j + 4] : 0.f;
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
-        u[j] = x0 + x1;
-      }
-      float w[2];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float x0 = u[2 * j], x1 = u[2 * j + 1];
-        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
-        w[j] = x0 + x1;
-      }
-#pragma unroll
-      for (int j = 0; j < 6; ++j) csum[j] = 0.f;
-      const int f0 = (fk & 1) + (fk >> 1) * 4;
-      float* row = static_cast<float*>(p.aux) + (size_t)(tm * 2 + wr) * N;
-      const int c0 = tn * N_BN + wc * 96 + 16 * f0 + fr;
-      if (c0 < N) row[c0] = w[0];
-      if (fk < 2 && c0 + 32 < N) row[c0 + 32] = w[1];
-    }
+    if constexpr (CS) cs_finish(csum, sc, r, p.aux, N, wr, wc, fr, fk);
   }
   // last tile: stores only (after the cursor's trailing DMAs have landed)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2009,107 +1884,109 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int pr = 0; pr < N_NST; ++pr) store_nth(acc, pr);
 }
 
+// ---- host dispatch ------------------------------------------------------------------------------------
+using Kern = void (*)(Args);
+// gemm4p_kernel's builds by layout (AKO, BKO, OT), with the flags each layout has
+template <typename T, bool BIAS, bool E, int LV = 0, bool GELU = false, bool RS = false, bool DAUX = false,
+          bool MUL = false, bool SKIPEPI = false>
+constexpr Kern k_nt() {
+  return gemm4p_kernel<T, false, false, false, BIAS, SKIPEPI, false, GELU, RS, E, LV, false, DAUX, MUL>;
+}
+template <typename T, bool BIAS, bool E, int LV = 0, bool CS = false, bool SPLIT = false>
+constexpr Kern k_tn() {
+  return gemm4p_kernel<T, true, true, false, BIAS, false, SPLIT, false, false, E, LV, CS>;
+}
+template <typename T, bool BIAS, bool E>
+constexpr Kern k_nn() {
+  return gemm4p_kernel<T, true, false, true, BIAS, false, false, false, false, E>;
+}
+// f(std::integral_constant<int, L>) for the L among LVS that equals lv; for L = 0 when none does
+template <int... LVS, typename F>
+void for_lv(int lv, F&& f) {
+  if (!((lv == LVS && (f(std::integral_constant<int, LVS>{}), true)) || ...)) f(std::integral_constant<int, 0>{});
+}
+
 template <typename T, bool BIAS, bool E>
 int launch_e(const Args& a, int ako, int bko, int trans, int grid, hipStream_t st) {
+  constexpr bool GELU = true, RS = true, DAUX = true, MUL = true, SKIPEPI = true, CS = true, SPLIT = true;
+  constexpr bool BF16 = std::is_same<T, bf16_t>::value;
+  const bool nt = !ako && !bko && !trans, tn = ako && bko && !trans, nn = ako && !bko && trans;
+  auto go = [&](Kern k) { hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, a); };
   if (a.splits > 1) {   // TN only (weight gradients)
-    if (!(ako && bko && !trans)) return (int)hipErrorInvalidValue;
+    if (!tn) return (int)hipErrorInvalidValue;
     bool cs = false;
     if constexpr (E) {
       if (a.epi & EPI_COLSUM) {
         cs = true;
-        hipLaunchKernelGGL((gemm4p_kernel<T, true, true, false, false, false, true, false, false, E, 0, true>), dim3(grid), dim3(256), 0, st, a);
+        go(k_tn<T, false, E, 0, CS, SPLIT>());
       }
     }
-    if (!cs) hipLaunchKernelGGL((gemm4p_kernel<T, true, true, false, false, false, true, false, false, E>), dim3(grid), dim3(256), 0, st, a);
+    if (!cs) go(k_tn<T, false, E, 0, !CS, SPLIT>());
     const long elems = (long)a.M * a.N;
     hipLaunchKernelGGL((splitk_reduce_kernel<T, BIAS>), dim3((unsigned)((elems / 8 + 255) / 256)), dim3(256), 0, st,
                        a.ws, static_cast<T*>(a.c), a.bias, a.M, a.N, a.ldc, a.splits);
     return (int)hipGetLastError();
   }
-  if constexpr (std::is_same<T, bf16_t>::value && !BIAS && !E) {   // measurement build (EPI_SKIP)
-    if ((a.epi & EPI_SKIP) && !ako && !bko && !trans) {
-      hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, false, true>), dim3(grid), dim3(256), 0, st, a);
+  if constexpr (BF16 && !BIAS && !E) {   // measurement build (EPI_SKIP)
+    if ((a.epi & EPI_SKIP) && nt) {
+      go(k_nt<T, false, false, 0, !GELU, !RS, !DAUX, !MUL, SKIPEPI>());
       return (int)hipGetLastError();
     }
   }
   if constexpr (!BIAS) {
-    if ((a.epi & EPI_ADEEP) && !(a.epi & (EPI_GELU | EPI_MULAUX)) && !ako && !bko && !trans && a.K >= 256) {
-      hipLaunchKernelGGL((gemm4a_kernel<T>), dim3(grid), dim3(256), 0, st, a);
+    if ((a.epi & EPI_ADEEP) && !(a.epi & (EPI_GELU | EPI_MULAUX)) && nt && a.K >= 256) {
+      go(gemm4a_kernel<T>);
       return (int)hipGetLastError();
     }
   }
-  if ((a.epi & EPI_RING) && !ako && !bko && !trans && a.K >= 128 && a.K % 64 == 0) {
-    if (a.epi & EPI_GELU)
-      hipLaunchKernelGGL((gemm4r_kernel<T, BIAS, true>), dim3(grid), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((gemm4r_kernel<T, BIAS, false>), dim3(grid), dim3(256), 0, st, a);
+  if ((a.epi & EPI_RING) && nt && a.K >= 128 && a.K % 64 == 0) {
+    if (a.epi & EPI_GELU) go(gemm4r_kernel<T, BIAS, true>);
+    else go(gemm4r_kernel<T, BIAS, false>);
     return (int)hipGetLastError();
   }
   // (pha_gemm4p_batched has checked: EPI_GELU_DAUX comes with GELU + bias, EPI_MULAUX without bias /
   // GELU / RSTAGE, both NT and not on the ring)
   if constexpr (BIAS) {
     if (a.epi & EPI_GELU_DAUX) {   // the bias + GELU epilogue with the derivative in aux, on its three hosts
-      if (!E && (a.epi & EPI_RSTAGE))
-        hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, true, false, false, true, true, false, 0, false, true>), dim3(grid), dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, true, false, false, true, false, E, 0, false, true>), dim3(grid), dim3(256), 0, st, a);
+      if (!E && (a.epi & EPI_RSTAGE)) go(k_nt<T, true, false, 0, GELU, RS, DAUX>());
+      else go(k_nt<T, true, E, 0, GELU, !RS, DAUX>());
       return (int)hipGetLastError();
     }
   } else {
     if (a.epi & EPI_MULAUX) {   // C = acc * aux; the early schedule in the plain NT default's PIN + SPREAD variant
-      hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, false, false, false, false, false, E, E ? 40 : 0, false, false, true>), dim3(grid), dim3(256), 0, st, a);
+      go(k_nt<T, false, E, E ? 40 : 0, !GELU, !RS, !DAUX, MUL>());
       return (int)hipGetLastError();
     }
   }
-  if (!E && (a.epi & EPI_RSTAGE) && !ako && !bko && !trans) {
-    if (a.epi & EPI_GELU)
-      hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, true, true>), dim3(grid), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, true>), dim3(grid), dim3(256), 0, st, a);
-  } else if ((a.epi & EPI_GELU) && !ako && !bko && !trans)
-    hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, true, false, E>), dim3(grid), dim3(256), 0, st, a);
-  else if (a.epi & EPI_GELU)
+  if (!E && (a.epi & EPI_RSTAGE) && nt) {
+    if (a.epi & EPI_GELU) go(k_nt<T, BIAS, false, 0, GELU, RS>());
+    else go(k_nt<T, BIAS, false, 0, !GELU, RS>());
+  } else if ((a.epi & EPI_GELU) && nt) {
+    go(k_nt<T, BIAS, E, 0, GELU>());
+  } else if (a.epi & EPI_GELU) {
     return (int)hipErrorInvalidValue;
-  else if (!ako && !bko && !trans) {
-    const int lv = E && std::is_same<T, bf16_t>::value
-                       ? ((a.epi >> EPI_LATE_SHIFT) & 15) | ((a.epi & EPI_WSTAG) ? 16 : 0) | (((a.epi >> EPI_SPREAD_SHIFT) & 3) << 5)
+  } else if (nt) {
+    int lv = E && BF16 ? ((a.epi >> EPI_LATE_SHIFT) & 15) | ((a.epi & EPI_WSTAG) ? 16 : 0) | (((a.epi >> EPI_SPREAD_SHIFT) & 3) << 5)
                        : 0;
-    if (lv == 40) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 40>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 72) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 72>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 104) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 104>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 47 && a.ws) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 47>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 8)hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 8>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 10) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 10>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 11) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 11>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 13) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 13>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 14) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 14>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 24) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 24>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 31 && a.ws) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 31>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 15 && a.ws) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 15>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 6) hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E, 6>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm4p_kernel<T, false, false, false, BIAS, false, false, false, false, E>), dim3(grid), dim3(256), 0, st, a);
-  }
-  else if (ako && bko && !trans) {
+    if (lv_stamp(lv) && !a.ws) lv = 0;   // the stamp builds (47, 31, 15) write to the workspace
+    for_lv<40, 72, 104, 47, 8, 10, 11, 13, 14, 24, 31, 15, 6>(lv, [&](auto L) { go(k_nt<T, BIAS, E, decltype(L)::value>()); });
+  } else if (tn) {
     // TN schedule variants (weight gradients): LV 8 (PIN) / 40 (PIN + SPREAD, the ops/gemm.py default:
     // 1.2-4.3 % on the GPT dW products, tools/tn_lv_ab.py)
-    const int lv = E && std::is_same<T, bf16_t>::value && !BIAS
-                       ? ((a.epi >> EPI_LATE_SHIFT) & 15) | (((a.epi >> EPI_SPREAD_SHIFT) & 3) << 5) : 0;
+    const int lv = E && BF16 && !BIAS ? ((a.epi >> EPI_LATE_SHIFT) & 15) | (((a.epi >> EPI_SPREAD_SHIFT) & 3) << 5) : 0;
+    bool cs = false;
     if constexpr (E) {
       if (a.epi & EPI_COLSUM) {
-        if (lv == 40) hipLaunchKernelGGL((gemm4p_kernel<T, true, true, false, BIAS, false, false, false, false, E, 40, true>), dim3(grid), dim3(256), 0, st, a);
-        else if (lv == 8) hipLaunchKernelGGL((gemm4p_kernel<T, true, true, false, BIAS, false, false, false, false, E, 8, true>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm4p_kernel<T, true, true, false, BIAS, false, false, false, false, E, 0, true>), dim3(grid), dim3(256), 0, st, a);
-        return (int)hipGetLastError();
+        cs = true;
+        for_lv<40, 8>(lv, [&](auto L) { go(k_tn<T, BIAS, E, decltype(L)::value, CS>()); });
       }
     }
-    if (lv == 40) hipLaunchKernelGGL((gemm4p_kernel<T, true, true, false, BIAS, false, false, false, false, E, 40>), dim3(grid), dim3(256), 0, st, a);
-    else if (lv == 8) hipLaunchKernelGGL((gemm4p_kernel<T, true, true, false, BIAS, false, false, false, false, E, 8>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm4p_kernel<T, true, true, false, BIAS, false, false, false, false, E>), dim3(grid), dim3(256), 0, st, a);
-  }
-  else if (ako && !bko && trans)
-    hipLaunchKernelGGL((gemm4p_kernel<T, true, false, true, BIAS, false, false, false, false, E>), dim3(grid), dim3(256), 0, st, a);
-  else
+    if (!cs) for_lv<40, 8>(lv, [&](auto L) { go(k_tn<T, BIAS, E, decltype(L)::value>()); });
+  } else if (nn) {
+    go(k_nn<T, BIAS, E>());
+  } else {
     return (int)hipErrorInvalidValue;
+  }
   return (int)hipGetLastError();
 }
 

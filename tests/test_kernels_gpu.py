@@ -1524,27 +1524,43 @@ def test_gemm4p_gelu_epilogue(M, N, K):
         assert err < 1e-2, (what, err)
 
 
-@pytest.mark.parametrize("layout", ["nt", "nt_bias", "nt_gelu", "tn", "tn_split", "nn"])
+@pytest.mark.parametrize("layout", ["nt", "nt_bias", "nt_gelu", "tn", "tn_split", "nn",
+                                    # the fp16 builds of the NT / NN defaults (the TN ones: test_tn_colsum_gpu.py)
+                                    "nt_fp16", "nt_bias_fp16", "nt_gelu_fp16", "nt_daux_fp16", "nt_adeep_fp16", "nn_fp16"])
 @pytest.mark.parametrize("M,N,K", [(264, 520, 128), (1032, 2056, 512), (2048, 1024, 1024), (296, 8, 64)])
 def test_gemm4p_early_schedule_bitwise(layout, M, N, K):
     """the early-release main loop (EPI_EARLY) changes only when operands are staged and waited for:
     outputs equal the default schedule's bit for bit (ragged tiles, bias, GELU aux, split-K, NN)"""
     from paddle_hackathon_amd.ops import gemm as G
     torch.manual_seed(5)
-    r = lambda *s: (torch.rand(*s, device="cuda") * 2 - 1).bfloat16()   # noqa: E731
+    dt = torch.float16 if layout.endswith("_fp16") else torch.bfloat16
+    layout = layout[:-5] if layout.endswith("_fp16") else layout
+    r = lambda *s: (torch.rand(*s, device="cuda") * 2 - 1).to(dt)   # noqa: E731
     if layout.startswith("nt"):
+        if layout == "nt_adeep":   # 3 A + 2 B slots: the default from K = 4096 on, taken from K = 256 on
+            K = max(K, 256)
         a, bt, bias = r(M, K), r(N, K), torch.randn(N, device="cuda")
-        if layout == "nt_gelu":
-            pre0, pre1 = (torch.empty(M, N, dtype=torch.bfloat16, device="cuda") for _ in range(2))
-            c0 = G.gemm_p(a, bt, bias=bias, gelu_aux=pre0)
-            c1 = G.gemm_p(a, bt, bias=bias, gelu_aux=pre1, epi_extra=G.EPI_EARLY)
+        if layout in ("nt_gelu", "nt_daux"):   # the aux: the pre-activation, or the GELU derivative
+            dv = layout == "nt_daux"
+            pre0, pre1 = (torch.empty(M, N, dtype=dt, device="cuda") for _ in range(2))
+            c0 = G.gemm_p(a, bt, bias=bias, gelu_aux=pre0, gelu_deriv=dv)
+            c1 = G.gemm_p(a, bt, bias=bias, gelu_aux=pre1, gelu_deriv=dv, epi_extra=G.EPI_EARLY)
             assert torch.equal(pre0, pre1)
+            # (both launches take the default schedule: the aux against fp32 is the check of its stores)
+            ref_aux = a.float() @ bt.float().t()
+            if dv:
+                x = (ref_aux + bias).requires_grad_(True)
+                ref_aux, = torch.autograd.grad(torch.nn.functional.gelu(x, approximate="tanh").sum(), x)
+            assert (pre1.float() - ref_aux).abs().max().item() <= 2e-2 * max(1.0, ref_aux.abs().max().item())
+        elif layout == "nt_adeep":
+            c0 = G.gemm_p(a, bt)
+            c1 = G.gemm_p(a, bt, epi_extra=G.EPI_EARLY | G.EPI_ADEEP)
         else:
             b = bias if layout == "nt_bias" else None
             c0 = G.gemm_p(a, bt, bias=b)
             c1 = G.gemm_p(a, bt, bias=b, epi_extra=G.EPI_EARLY)
-        ref = a.float() @ bt.float().t() + (bias if layout != "nt" else 0)
-        if layout == "nt_gelu":
+        ref = a.float() @ bt.float().t() + (bias if layout not in ("nt", "nt_adeep") else 0)
+        if layout in ("nt_gelu", "nt_daux"):
             ref = torch.nn.functional.gelu(ref, approximate="tanh")
     elif layout.startswith("tn"):
         if K < 256 and layout == "tn_split":
