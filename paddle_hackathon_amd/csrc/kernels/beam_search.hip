@@ -16,35 +16,29 @@
 //
 // Two launches; the kernel boundary between them is the only inter-workgroup hand-off:
 //  1. beam_cand_kernel, one workgroup of 1024 threads per row: the row is staged in LDS as 16-bit
-//     order-preserving keys (as sampling.hip does), the K-th largest key is found with two count
+//     order-preserving keys (logit_keys.h), the K-th largest key is found with two count
 //     histograms (upper 11 bits, then the lower 5 inside the boundary bin), and the row's K best
 //     candidates go to a workspace in order: descending key, ascending index among equal keys, of the
 //     boundary key the lowest indices. Within a row the order of totals is the order of keys, so no
 //     other token of the row can be among the group's K best. A candidate carries
-//     lp = (val - xmax) - logf(Z * 2^-40), Z the fixed-point normaliser of sampling.hip: a K = 1 step
-//     scores a token exactly as greedy search does.
+//     lp = (val - xmax) - logf(Z * 2^-40), Z the fixed-point normaliser sampling.hip sums from the
+//     same qfix: a K = 1 step scores a token exactly as greedy search does.
 //  2. beam_merge_kernel, one workgroup per group: the K * K <= 256 candidates become cum + lp in fp32,
 //     each finds its rank by counting the candidates ahead of it, the first K write the six outputs
 //     (cum, finished and len are read into LDS before the barrier that precedes the first store), and
 //     the workgroup then re-indexes the group's table in place: one thread owns one column t, reads
 //     its K entries (into LDS slots of its own) and writes its K entries.
-#include "common.h"
+#include "logit_keys.h"
 
 namespace pha {
 namespace beam {
 
-typedef unsigned long long u64;
+using namespace lk;
 
-constexpr int THREADS = 1024, WAVES = THREADS / 64;
-constexpr int MAX_V = 65536, MAX_R = 16, MAX_K = 16;
+constexpr int MAX_R = 16, MAX_K = 16;
 constexpr int MERGE_THREADS = MAX_K * MAX_K;   // one thread per candidate of a group
-constexpr int L2_BITS = 5, L1_BINS = 1 << (16 - L2_BITS), L2_BINS = 1 << L2_BITS;
-constexpr float FIX_ONE = 1099511627776.f;   // 2^40
 
-struct Found {
-  unsigned count_above;
-  int bin;
-};
+typedef lk::Found<false> Found;   // the scans run on counts alone: no mass arrays in LDS
 
 struct Smem {
   u64 wt[WAVES];
@@ -58,68 +52,6 @@ struct Smem {
 };
 static_assert(sizeof(Smem) % 16 == 0, "the keys behind it are stored 16 bytes at a time");
 static_assert(sizeof(Smem) + 2 * MAX_V <= 160 * 1024, "one workgroup's LDS");
-
-// larger logit <=> larger key; -0 and +0 are one logit and get one key (sampling.hip's mapping)
-__device__ __forceinline__ unsigned key_of(unsigned b) {
-  if ((b & 0x7fffu) == 0u) b = 0u;
-  return (b & 0x8000u) ? (~b & 0xffffu) : (b | 0x8000u);
-}
-template <typename T> __device__ __forceinline__ float val_of(unsigned key);
-template <> __device__ __forceinline__ float val_of<bf16_t>(unsigned key) {
-  const unsigned b = (key & 0x8000u) ? (key ^ 0x8000u) : (~key & 0xffffu);
-  return bf16_to_f32((uint16_t)b);
-}
-template <> __device__ __forceinline__ float val_of<half_t>(unsigned key) {
-  const unsigned b = (key & 0x8000u) ? (key ^ 0x8000u) : (~key & 0xffffu);
-  return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
-}
-
-// the mass of a token in 2^-40 units of the largest one (sampling.hip's qfix at temperature 1)
-template <typename T>
-__device__ __forceinline__ u64 qfix(unsigned key, float xmax) {
-  return (u64)(__expf((val_of<T>(key) - xmax) * 1.f) * FIX_ONE);
-}
-
-// exclusive prefix of v over the block in thread order, and the block's total; ends on a barrier
-__device__ __forceinline__ u64 block_scan(u64 v, u64* wt, u64* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  u64 inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const u64 n = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += n;
-  }
-  if (lane == 63) wt[wid] = inc;
-  __syncthreads();
-  u64 base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < WAVES; ++w) {
-    const u64 x = wt[w];
-    if (w < wid) base += x;
-    tot += x;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
-// Walk the bins from the highest down and stop in the one where the running count first reaches
-// target: 1 <= target <= the total. Thread t owns the bins at descending positions 2t, 2t + 1.
-__device__ __forceinline__ Found scan_find(const unsigned* cnt, int nbins, u64 target, Smem& sm) {
-  const int b0 = nbins - 1 - 2 * (int)threadIdx.x, b1 = b0 - 1;
-  const u64 c0 = b0 >= 0 ? cnt[b0] : 0u, c1 = b1 >= 0 ? cnt[b1] : 0u;
-  u64 tot;
-  const u64 e = block_scan(c0 + c1, sm.wt, &tot);
-  if (b0 >= 0 && e < target && target <= e + c0) {
-    sm.found.count_above = (unsigned)e; sm.found.bin = b0;
-  } else if (b1 >= 0 && e + c0 < target && target <= e + c0 + c1) {
-    sm.found.count_above = (unsigned)(e + c0); sm.found.bin = b1;
-  }
-  __syncthreads();
-  const Found f = sm.found;
-  __syncthreads();
-  return f;
-}
 
 // cand_lp / cand_tok: [R, MAX_K]; slot j >= (what the row has) holds (-inf, V + j)
 template <typename T>
@@ -143,42 +75,20 @@ __global__ __launch_bounds__(THREADS) void beam_cand_kernel(const T* __restrict_
   }
   const int Kr = K < V ? K : V;   // candidates the row has
 
-  // ---- stage the row as keys, find the largest ----------------------------------------------------
+  // ---- stage the row as keys, find the largest (block_max's barrier publishes the zeroes too) ------
   const unsigned short* src = reinterpret_cast<const unsigned short*>(logits + (long)row * ld);
-  unsigned kmax = 0u;
-  const int vend = vec ? (V & ~7) : 0;
-  for (int c = tid * 8; c < vend; c += THREADS * 8) {
-    const uint4 r = *reinterpret_cast<const uint4*>(src + c);
-    unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const unsigned lo = key_of(w[j] & 0xffffu), hi = key_of(w[j] >> 16);
-      kmax = max(kmax, max(lo, hi));
-      w[j] = lo | (hi << 16);
-    }
-    *reinterpret_cast<uint4*>(keys + c) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  for (int c = vend + tid; c < V; c += THREADS) {
-    const unsigned k = key_of(src[c]);
-    kmax = max(kmax, k);
-    keys[c] = (unsigned short)k;
-  }
+  unsigned kmax = stage_keys(src, keys, V, vec);
   for (int b = tid; b < L1_BINS; b += THREADS) sm.cnt1[b] = 0u;
   if (tid < L2_BINS) sm.cnt2[tid] = 0u;
   if (tid == 0) { sm.found.count_above = 0u; sm.found.bin = 0; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o, 64));
-  if (lane == 0) sm.kmax[wid] = kmax;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < WAVES; ++w) kmax = max(kmax, sm.kmax[w]);
+  kmax = block_max(kmax, sm.kmax, lane, wid);
   const float xmax = val_of<T>(kmax);
 
   // ---- the normaliser and the first-level histogram -----------------------------------------------
   u64 zloc = 0;
   for (int i = tid; i < V; i += THREADS) {
     const unsigned k = keys[i];
-    zloc += qfix<T>(k, xmax);
+    zloc += qfix<T>(k, xmax, 1.f);   // temperature 1: x * 1.f is exact
     if (Kr > 1) atomicAdd(&sm.cnt1[k >> L2_BITS], 1u);
   }
   u64 Z;
@@ -188,21 +98,20 @@ __global__ __launch_bounds__(THREADS) void beam_cand_kernel(const T* __restrict_
   unsigned kt = kmax;
   u64 rt = 1;
   if (Kr > 1) {
-    const Found f1 = scan_find(sm.cnt1, L1_BINS, (u64)Kr, sm);
+    const Found f1 = scan_find<false>(sm.cnt1, nullptr, L1_BINS, false, (u64)Kr, sm.wt, &sm.found);
     for (int i = tid; i < V; i += THREADS) {
       const unsigned k = keys[i];
       if ((k >> L2_BITS) == (unsigned)f1.bin) atomicAdd(&sm.cnt2[k & (L2_BINS - 1)], 1u);
     }
     __syncthreads();
-    const Found f2 = scan_find(sm.cnt2, L2_BINS, (u64)Kr - f1.count_above, sm);
+    const Found f2 = scan_find<false>(sm.cnt2, nullptr, L2_BINS, false, (u64)Kr - f1.count_above, sm.wt, &sm.found);
     kt = ((unsigned)f1.bin << L2_BITS) | (unsigned)f2.bin;
     rt = (u64)Kr - f1.count_above - f2.count_above;
   }
 
   // ---- collect the Kr candidates in ascending token index: thread t owns one contiguous chunk ------
-  int chunk = (V + THREADS - 1) / THREADS;
-  chunk += (6 - (chunk & 3)) & 3;   // chunk % 4 == 2: an odd stride in LDS words, no bank conflict
-  const int i0 = min(tid * chunk, V), i1 = min(i0 + chunk, V);
+  const Chunk ch = row_chunk(V);
+  const int i0 = ch.i0, i1 = ch.i1;
   unsigned ties = 0u, gt = 0u;
   for (int i = i0; i < i1; ++i) {
     const unsigned k = keys[i];
@@ -211,7 +120,7 @@ __global__ __launch_bounds__(THREADS) void beam_cand_kernel(const T* __restrict_
   }
   u64 tot;
   const u64 tb = block_scan((u64)ties, sm.wt, &tot);
-  const u64 take = tb >= rt ? 0 : (rt - tb < (u64)ties ? rt - tb : (u64)ties);
+  const u64 take = ties_taken(tb, ties, rt);
   u64 slot = block_scan((u64)gt + take, sm.wt, &tot);   // tot == Kr
   if (gt + take > 0) {
     u64 tr = tb;
@@ -331,16 +240,11 @@ static int launch(const void* logits, long ld, float* cum, unsigned char* finish
                   float* lp_out, int* ind, const int* ts_rows, float* cand_lp, int* cand_tok, int R, int V, int K,
                   long eos, int max_seq,
                   hipStream_t st) {
-  const size_t lds = sizeof(Smem) + 2 * (size_t)((V + 7) / 8 * 8);
   static bool attr = false;
-  if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)beam_cand_kernel<T>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(sizeof(Smem) + 2 * MAX_V));
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  const int vec = ((uintptr_t)logits % 16 == 0 && ld % 8 == 0) ? 1 : 0;
+  size_t lds;
+  int vec;
+  const int e = keyed_launch(beam_cand_kernel<T>, attr, sizeof(Smem), logits, ld, V, &lds, &vec);
+  if (e != (int)hipSuccess) return e;
   hipLaunchKernelGGL(beam_cand_kernel<T>, dim3(R), dim3(THREADS), lds, st, (const T*)logits, ld, finished, cand_lp,
                      cand_tok, V, K, eos, vec);
   hipLaunchKernelGGL(beam_merge_kernel, dim3(R / K), dim3(MERGE_THREADS), 0, st, cand_lp, cand_tok, cum, finished, len,
@@ -352,7 +256,7 @@ static int launch(const void* logits, long ld, float* cum, unsigned char* finish
 }  // namespace pha
 
 // rows and beams per call, and the largest vocabulary (sampling.hip's limit, for the same reason)
-PHA_API int pha_beam_search_max_v() { return pha::beam::MAX_V; }
+PHA_API int pha_beam_search_max_v() { return pha::lk::MAX_V; }
 PHA_API int pha_beam_search_max_k() { return pha::beam::MAX_K; }
 
 // logits [R, V] bf16 / fp16 with row stride ld (elements) and unit inner stride; cum [R] fp32, finished
@@ -365,7 +269,7 @@ PHA_API int pha_beam_search_step(int dt, const void* logits, long ld, float* cum
                                  float* cand_lp, int* cand_tok, int R, int V, int K, long eos, int max_seq, hipStream_t stream) {
   if (!logits || !cum || !finished || !len || !tok || !parent || !logprob || !ind || !ts_rows || !cand_lp || !cand_tok)
     return (int)hipErrorInvalidValue;
-  if (R < 1 || R > pha::beam::MAX_R || V < 2 || V > pha::beam::MAX_V || ld < V || max_seq < 1)
+  if (R < 1 || R > pha::beam::MAX_R || V < 2 || V > pha::lk::MAX_V || ld < V || max_seq < 1)
     return (int)hipErrorInvalidValue;
   if (K < 1 || K > pha::beam::MAX_K || K > V || R % K != 0) return (int)hipErrorInvalidValue;
   if (dt == pha::kBF16)

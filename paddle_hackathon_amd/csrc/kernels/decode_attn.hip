@@ -293,39 +293,22 @@ __global__ void decode_attn_combine(const float* __restrict__ ws, T* __restrict_
   Cvt<T>::st(out, bh * D + d, L > 0.f ? acc / L : 0.f);   // every key masked out: zeros
 }
 
-template <typename T, bool ROWS>
+// ind / beam: the beam form's table and group size; the plain forms pass null and 1
+template <typename T, bool ROWS, bool BEAM>
 static int decode_attn_launch(const void* qkv, const void* bias, void* cache, const float* mask, long msb, long msh,
-                              float scale, int ts, const int* ts_dev, void* out, float* ws, int B, int H, int D,
-                              int max_seq, hipStream_t st) {
+                              float scale, int ts, const int* ts_dev, const int* ind, int beam, void* out, float* ws,
+                              int B, int H, int D, int max_seq, hipStream_t st) {
   const int nsplit = (max_seq + DECODE_ATTN_CHUNK - 1) / DECODE_ATTN_CHUNK;
   const dim3 grid(nsplit, H, B);
 #define PHA_DA_LAUNCH(DD)                                                                                \
-  decode_attn_partial<T, DD, ROWS, false><<<grid, DECODE_ATTN_THREADS, 0, st>>>(                         \
+  decode_attn_partial<T, DD, ROWS, BEAM><<<grid, DECODE_ATTN_THREADS, 0, st>>>(                          \
       (const T*)qkv, (const T*)bias, (T*)cache, mask, msb, msh, scale, ts, ts_dev, ws, B, H, max_seq, nsplit, \
-      nullptr, 1)
-  if (D == 32) PHA_DA_LAUNCH(32);
-  else if (D == 64) PHA_DA_LAUNCH(64);
-  else PHA_DA_LAUNCH(128);
-#undef PHA_DA_LAUNCH
-  decode_attn_combine<T, ROWS><<<dim3(H, B), D, 0, st>>>(ws, (T*)out, ts, ts_dev, H, D, max_seq, nsplit);
-  return (int)hipGetLastError();
-}
-
-template <typename T>
-static int decode_attn_beam_launch(const void* qkv, const void* bias, void* cache, const float* mask, long msb, long msh,
-                                   float scale, const int* ts_rows, const int* ind, int beam, void* out, float* ws,
-                                   int B, int H, int D, int max_seq, hipStream_t st) {
-  const int nsplit = (max_seq + DECODE_ATTN_CHUNK - 1) / DECODE_ATTN_CHUNK;
-  const dim3 grid(nsplit, H, B);
-#define PHA_DA_LAUNCH(DD)                                                                                \
-  decode_attn_partial<T, DD, true, true><<<grid, DECODE_ATTN_THREADS, 0, st>>>(                          \
-      (const T*)qkv, (const T*)bias, (T*)cache, mask, msb, msh, scale, 0, ts_rows, ws, B, H, max_seq, nsplit, \
       ind, beam)
   if (D == 32) PHA_DA_LAUNCH(32);
   else if (D == 64) PHA_DA_LAUNCH(64);
   else PHA_DA_LAUNCH(128);
 #undef PHA_DA_LAUNCH
-  decode_attn_combine<T, true><<<dim3(H, B), D, 0, st>>>(ws, (T*)out, 0, ts_rows, H, D, max_seq, nsplit);
+  decode_attn_combine<T, ROWS><<<dim3(H, B), D, 0, st>>>(ws, (T*)out, ts, ts_dev, H, D, max_seq, nsplit);
   return (int)hipGetLastError();
 }
 
@@ -343,11 +326,11 @@ PHA_API int pha_decode_attn(int dt, const void* qkv, const void* qkv_bias, void*
     return (int)hipErrorInvalidValue;
   if (!ts_dev && (ts < 0 || ts >= max_seq)) return (int)hipErrorInvalidValue;
   if (dt == pha::kBF16)
-    return pha::decode_attn_launch<pha::bf16_t, false>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts, ts_dev, out,
-                                                ws, B, H, D, max_seq, stream);
+    return pha::decode_attn_launch<pha::bf16_t, false, false>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts,
+                                                              ts_dev, nullptr, 1, out, ws, B, H, D, max_seq, stream);
   if (dt == pha::kF16)
-    return pha::decode_attn_launch<pha::half_t, false>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts, ts_dev, out,
-                                                ws, B, H, D, max_seq, stream);
+    return pha::decode_attn_launch<pha::half_t, false, false>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts,
+                                                              ts_dev, nullptr, 1, out, ws, B, H, D, max_seq, stream);
   return (int)hipErrorInvalidValue;
 }
 
@@ -359,11 +342,11 @@ PHA_API int pha_decode_attn_rows(int dt, const void* qkv, const void* qkv_bias, 
   if (B <= 0 || H <= 0 || max_seq <= 0 || B > 65535 || H > 65535 || (D != 32 && D != 64 && D != 128) || !ts_rows)
     return (int)hipErrorInvalidValue;
   if (dt == pha::kBF16)
-    return pha::decode_attn_launch<pha::bf16_t, true>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0, ts_rows,
-                                                      out, ws, B, H, D, max_seq, stream);
+    return pha::decode_attn_launch<pha::bf16_t, true, false>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0,
+                                                             ts_rows, nullptr, 1, out, ws, B, H, D, max_seq, stream);
   if (dt == pha::kF16)
-    return pha::decode_attn_launch<pha::half_t, true>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0, ts_rows,
-                                                      out, ws, B, H, D, max_seq, stream);
+    return pha::decode_attn_launch<pha::half_t, true, false>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0,
+                                                             ts_rows, nullptr, 1, out, ws, B, H, D, max_seq, stream);
   return (int)hipErrorInvalidValue;
 }
 
@@ -377,10 +360,10 @@ PHA_API int pha_decode_attn_beam(int dt, const void* qkv, const void* qkv_bias, 
     return (int)hipErrorInvalidValue;
   if (beam < 1 || B % beam != 0) return (int)hipErrorInvalidValue;
   if (dt == pha::kBF16)
-    return pha::decode_attn_beam_launch<pha::bf16_t>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts_rows, ind,
-                                                     beam, out, ws, B, H, D, max_seq, stream);
+    return pha::decode_attn_launch<pha::bf16_t, true, true>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0,
+                                                            ts_rows, ind, beam, out, ws, B, H, D, max_seq, stream);
   if (dt == pha::kF16)
-    return pha::decode_attn_beam_launch<pha::half_t>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, ts_rows, ind,
-                                                     beam, out, ws, B, H, D, max_seq, stream);
+    return pha::decode_attn_launch<pha::half_t, true, true>(qkv, qkv_bias, cache, mask, mask_sb, mask_sh, scale, 0,
+                                                            ts_rows, ind, beam, out, ws, B, H, D, max_seq, stream);
   return (int)hipErrorInvalidValue;
 }

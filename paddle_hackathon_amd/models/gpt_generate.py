@@ -47,39 +47,36 @@ STRATEGIES = ("greedy_search", "sampling", "beam_search")
 EOS_CHECK_EVERY = 16   # decode steps between two host reads of finished.all()
 
 
-class _GraphState:
-    """the static buffers of one captured decode step, and the graph once it exists"""
+class _State:
+    """the static buffers of one decode step over R rows (the batch, or batch * beams for beam search),
+    and its captured graph once that exists"""
 
-    def __init__(self, B, cache_len, cfg, dtype, device, ragged=False):
+    def __init__(self, R, cache_len, cfg, dtype, device, ts_per_row, beam):
         H, D = cfg.num_heads, cfg.head_dim
-        self.caches = [torch.zeros(2, B, H, cache_len, D, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
-        self.tok = torch.zeros(B, dtype=torch.int64, device=device)
-        self.ts = torch.zeros(B if ragged else 1, dtype=torch.int32, device=device)   # ragged: a step per row
-        self.u = torch.zeros(B, dtype=torch.float32, device=device)
-        self.finished = torch.zeros(B, dtype=torch.uint8, device=device)
-        self.ids = self.logprob = None
+
+        def zeros(dt, *shape):
+            return torch.zeros(*shape, dtype=dt, device=device)
+        self.caches = [zeros(dtype, 2, R, H, cache_len, D) for _ in range(cfg.num_layers)]
+        self.tok = zeros(torch.int64, R)
+        self.ts = zeros(torch.int32, R if ts_per_row else 1)   # one element: every row is at the same step
+        self.finished = zeros(torch.uint8, R)
+        self.u = self.cum = self.lens = self.ind = None
+        if beam:
+            self.cum, self.lens = zeros(torch.float32, R), zeros(torch.int32, R)
+            self.ind = zeros(torch.int32, R, cache_len)   # the cache-indirection table
+            carried = (self.tok, self.ts, self.cum, self.finished, self.lens, self.ind)
+        else:
+            self.u = zeros(torch.float32, R)   # rewritten before every step, so not carried
+            carried = (self.tok, self.finished, self.ts)
+        self.carried = carried   # what a step replaces: saved before the warm-up step, put back after it and after capture
+        self.out = None   # what the captured step returned: the tensors a replay fills
         self.graph = None
         self.weights_at = None
 
-
-class _BeamState:
-    """the static buffers of one captured beam-search step (R = B * K rows), and the graph once it exists"""
-
-    def __init__(self, B, K, cache_len, cfg, dtype, device):
-        H, D, R = cfg.num_heads, cfg.head_dim, B * K
-        self.caches = [torch.zeros(2, R, H, cache_len, D, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
-        self.tok = torch.zeros(R, dtype=torch.int64, device=device)
-        self.ts = torch.zeros(R, dtype=torch.int32, device=device)        # always a step per row
-        self.cum = torch.zeros(R, dtype=torch.float32, device=device)
-        self.finished = torch.zeros(R, dtype=torch.uint8, device=device)
-        self.lens = torch.zeros(R, dtype=torch.int32, device=device)
-        self.ind = torch.zeros(R, cache_len, dtype=torch.int32, device=device)   # the cache-indirection table
-        self.out = None
-        self.graph = None
-        self.weights_at = None
-
-    def state(self):
-        return (self.tok, self.ts, self.cum, self.finished, self.lens, self.ind)
+    def reset(self):
+        """a kept state before its next call"""
+        for t in self.caches + [self.finished] + ([] if self.ind is None else [self.lens, self.ind]):
+            t.zero_()
 
 
 class GPTGenerator:
@@ -88,8 +85,8 @@ class GPTGenerator:
     def __init__(self, model):
         self.model = model
         self._qkv = {}        # layer index -> (weight version, bias version, repacked weight, repacked bias)
-        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged) -> _GraphState;
-        #                       (B, cache length, "beam_search", num_beams, eos) -> _BeamState
+        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged) -> _State;
+        #                       (B, cache length, "beam_search", num_beams, eos) -> _State
         self._eager = set()   # keys whose warm-up step left the kernel path: not tried again
         self.captures = 0     # hipGraph captures so far (a second generate call adds none)
         self.last_caches = None
@@ -157,26 +154,19 @@ class GPTGenerator:
         return _ops.hip.sample_logits(*args)
 
     def _step(self, weights, st, s, host_ts=None):
-        """one token: reads st.tok / st.ts / st.u, appends to st.caches, writes the new token to st.tok,
-        advances st.ts; returns (ids, logprob)"""
+        """one token: reads st.tok / st.ts, appends to st.caches (through st.ind where the state has a
+        table), picks with st.u (sampling: returns (ids, logprob)) or replaces the beam state (beam search:
+        returns (token, parent, logprob)), writes the new token to st.tok and advances st.ts"""
         emb = self.model.gpt.embeddings
         x = _ops.fused.embedding(st.tok, emb.word_embeddings.weight._t) \
             + emb.position_embeddings.weight._t.index_select(0, st.ts)
-        h = self._stack(x.unsqueeze(1), weights, st.caches, st.ts if host_ts is None else host_ts)
-        ids, lp = self._sample(self._logits(h.reshape(h.shape[0], -1)), st.u, st.finished, s)
-        st.tok.copy_(ids)
-        st.ts.add_(1)
-        return ids, lp
-
-    def _beam_step(self, weights, st, s):
-        """one beam-search token: reads st.tok / st.ts and the beam state, appends to st.caches through
-        st.ind, replaces the beam state and st.tok, advances st.ts; returns (token, parent, logprob)"""
-        emb = self.model.gpt.embeddings
-        x = _ops.fused.embedding(st.tok, emb.word_embeddings.weight._t) \
-            + emb.position_embeddings.weight._t.index_select(0, st.ts)
-        h = self._stack(x.unsqueeze(1), weights, st.caches, st.ts, cache_indirection=st.ind, beam_size=s["beams"])
-        out = _ops.hip.beam_search_step(self._logits(h.reshape(h.shape[0], -1)), st.cum, st.finished, st.lens,
-                                        s["eos"], s["beams"], st.ind, st.ts)
+        beam = {} if st.ind is None else dict(cache_indirection=st.ind, beam_size=s["beams"])
+        h = self._stack(x.unsqueeze(1), weights, st.caches, st.ts if host_ts is None else host_ts, **beam)
+        logits = self._logits(h.reshape(h.shape[0], -1))
+        if st.ind is None:
+            out = self._sample(logits, st.u, st.finished, s)
+        else:
+            out = _ops.hip.beam_search_step(logits, st.cum, st.finished, st.lens, s["eos"], s["beams"], st.ind, st.ts)
         st.tok.copy_(out[0])
         st.ts.add_(1)
         return out
@@ -326,16 +316,7 @@ class GPTGenerator:
             return self._generate_beam(ids_in, lens, n_new, s, use_graph)
         key = (B, cache_len, s["strategy"], s["temperature"], s["top_k"], s["top_p"], s["eos"], s["pad"], ragged)
         weights = self._layer_weights()
-        want_graph = wte.is_cuda and use_graph is not False and n_new > 1 \
-            and (bool(use_graph) or key not in self._eager)
-        st = self._graphs.get(key) if want_graph else None
-        if st is None:
-            st = _GraphState(B, cache_len, cfg, dtype, dev, ragged)
-        else:
-            for c in st.caches:
-                c.zero_()
-            st.finished.zero_()
-        self.last_caches = st.caches
+        st, want_graph = self._state_for(key, B, cache_len, ragged, False, use_graph, n_new)
 
         # uniforms of every step, drawn up front (no per-step generator state in a captured graph)
         gen = None
@@ -358,69 +339,88 @@ class GPTGenerator:
         ids, lp = self._sample(self._logits(last.contiguous()), U[0].contiguous(), st.finished, s)
         out_ids[:, 0], out_lp[:, 0] = ids, lp
         st.tok.copy_(ids)
-        self._set_ts(st, ts0)
+        if ragged:
+            st.ts.copy_(ts0)   # the int32 [B] lengths
+        else:
+            st.ts.fill_(ts0)
+        # on the CPU the composite takes a uniform step as a Python int (per-row steps stay a tensor)
+        self._decode(key, st, weights, s, want_graph, bool(use_graph), n_new, (out_ids.t(), out_lp.t()), U=U,
+                     host_ts=None if wte.is_cuda or ragged else P)
+        return _wrap(out_ids), _wrap(out_lp)
 
+    def _state_for(self, key, R, cache_len, ts_per_row, beam, use_graph, n_new):
+        """(state, want_graph): whether this call is to replay a captured step, and its state: the one
+        kept under ``key`` with its graph, reset, or a new one"""
+        wte = self.model.gpt.embeddings.word_embeddings.weight._t
+        want_graph = wte.is_cuda and use_graph is not False and n_new > 1 \
+            and (bool(use_graph) or key not in self._eager)
+        st = self._graphs.get(key) if want_graph else None
+        if st is None:
+            st = _State(R, cache_len, self.model.cfg, wte.dtype, wte.device, ts_per_row, beam)
+        else:
+            st.reset()
+        self.last_caches = st.caches
+        return st, want_graph
+
+    def _decode(self, key, st, weights, s, want_graph, required, n_new, outs, U=None, host_ts=None):
+        """the decode steps 1 .. n_new - 1 from a state that holds the first token and its step: on the
+        captured graph where ``want_graph`` and the capture succeeds or is ``required`` (the state is then
+        kept under ``key``), eagerly otherwise. Element
+        i of step j's result goes to ``outs[i][j]``; ``U[j]`` are the step's uniforms. Returns the number of
+        leading entries of ``outs`` that are filled (fewer than n_new after an early stop)."""
         graph = None
         if want_graph:
-            graph = self._graph_for(st, weights, s, ts0, required=bool(use_graph))
+            graph = self._graph_for(st, weights, s, required)
             if graph is not None:
                 self._graphs[key] = st
             else:
                 self._eager.add(key)
-        # on the CPU the composite takes a uniform step as a Python int (per-row steps stay a tensor)
-        host_ts = None if wte.is_cuda or ragged else P
-        self.last_steps = 0
+        self.last_steps, T = 0, 1
         for j in range(1, n_new):
             self.last_steps = j
-            st.u.copy_(U[j])
+            if U is not None:
+                st.u.copy_(U[j])
             if graph is not None:
                 graph.replay()
-                ids, lp = st.ids, st.logprob
+                out = st.out
             else:
-                ids, lp = self._step(weights, st, s, host_ts)
+                out = self._step(weights, st, s, host_ts)
                 if host_ts is not None:
                     host_ts += 1
-            out_ids[:, j], out_lp[:, j] = ids, lp
+            for o, v in zip(outs, out):
+                o[j] = v
+            T = j + 1
             if s["eos"] >= 0 and j % EOS_CHECK_EVERY == 0 and bool(st.finished.all()):
                 break
-        return _wrap(out_ids), _wrap(out_lp)
+        return T
 
-    @staticmethod
-    def _set_ts(st, ts0):
-        """the first decode step: the prompt length, or the int32 [B] lengths of a ragged call"""
-        if isinstance(ts0, torch.Tensor):
-            st.ts.copy_(ts0)
-        else:
-            st.ts.fill_(ts0)
-
-    def _graph_for(self, st, weights, s, ts0, required):
+    def _graph_for(self, st, weights, s, required):
         """the captured step of ``st`` (captured now if it is new or the weights moved), or None where
         the warm-up step shows that a piece of it left the kernel path and the graph was not required"""
         at = tuple(t.data_ptr() for group in weights for t in group)
         if st.graph is not None and st.weights_at == at:
             return st.graph
         from ..ops import fallback
-        keep = (st.tok.clone(), st.finished.clone())
+        keep = [t.clone() for t in st.carried]
         before = fallback.total()
         self._step(weights, st, s)   # warm-up: what it appends at the first step is rewritten by the first replay
+        # the sampling composite is captured like the kernel; the beam composite is not
         clean = fallback.total() == before and os.environ.get("PHA_DECODE_ATTN", "1") != "0" \
+            and (st.ind is None or os.environ.get("PHA_BEAM_KERNEL", "1") != "0") \
             and st.caches[0].dtype in (torch.bfloat16, torch.float16) and self.model.cfg.head_dim in (32, 64, 128)
-        st.tok.copy_(keep[0])
-        st.finished.copy_(keep[1])
-        self._set_ts(st, ts0)
+        for t, k in zip(st.carried, keep):
+            t.copy_(k)
         if not clean and not required:
-            for c in st.caches:
-                if isinstance(ts0, torch.Tensor):
-                    c[:, torch.arange(c.shape[1], device=c.device), :, ts0.long()] = 0
-                else:
-                    c[:, :, :, ts0].zero_()
+            for c in st.caches:   # what the warm-up step appended, at each row's first step
+                c[:, torch.arange(c.shape[1], device=c.device), :, st.ts.long().expand(c.shape[1])] = 0
             return None
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            st.ids, st.logprob = self._step(weights, st, s)
+            st.out = self._step(weights, st, s)
         self.captures += 1
-        self._set_ts(st, ts0)   # capture launches nothing: the first replay is step 0
+        for t, k in zip(st.carried, keep):   # capture launches nothing: the first replay is step 0
+            t.copy_(k)
         st.graph, st.weights_at = g, at
         return g
 
@@ -428,25 +428,13 @@ class GPTGenerator:
     def _generate_beam(self, ids_in, lens, n_new, s, use_graph):
         """generate()'s beam-search branch: ``ids_in`` [B, P] on the device, ``lens`` the prompt
         lengths or None"""
-        model, cfg = self.model, self.model.cfg
-        wte = model.gpt.embeddings.word_embeddings.weight._t
-        dev, dtype = wte.device, wte.dtype
+        model, dev = self.model, ids_in.device
         B, P = ids_in.shape
         K, eos = s["beams"], s["eos"]
         R, cache_len = B * K, P + n_new
         key = (B, cache_len, "beam_search", K, eos)
         weights = self._layer_weights()
-        want_graph = wte.is_cuda and use_graph is not False and n_new > 1 \
-            and (bool(use_graph) or key not in self._eager)
-        st = self._graphs.get(key) if want_graph else None
-        if st is None:
-            st = _BeamState(B, K, cache_len, cfg, dtype, dev)
-        else:
-            for c in st.caches:
-                c.zero_()
-            for t in (st.finished, st.lens, st.ind):
-                t.zero_()
-        self.last_caches = st.caches
+        st, want_graph = self._state_for(key, R, cache_len, True, True, use_graph, n_new)
         # per group: beam 0 starts at 0, the others at -inf, so the first step's K picks all continue beam 0
         st.cum.copy_(torch.tensor([0.0] + [float("-inf")] * (K - 1), dtype=torch.float32).repeat(B))
 
@@ -469,26 +457,7 @@ class GPTGenerator:
         toks[0], pars[0], lps[0] = tok, parent, lp
         st.tok.copy_(tok)
         st.ts.copy_(ts0)
-
-        graph = None
-        if want_graph:
-            graph = self._beam_graph_for(st, weights, s, ts0, required=bool(use_graph))
-            if graph is not None:
-                self._graphs[key] = st
-            else:
-                self._eager.add(key)
-        self.last_steps, T = 0, 1
-        for j in range(1, n_new):
-            self.last_steps = j
-            if graph is not None:
-                graph.replay()
-                tok, parent, lp = st.out
-            else:
-                tok, parent, lp = self._beam_step(weights, st, s)
-            toks[j], pars[j], lps[j] = tok, parent, lp
-            T = j + 1
-            if eos >= 0 and j % EOS_CHECK_EVERY == 0 and bool(st.finished.all()):
-                break
+        T = self._decode(key, st, weights, s, want_graph, bool(use_graph), n_new, (toks, pars, lps))
 
         # back-trace the K histories, rank each group, keep the first nret
         from ..nn.functional.common import gather_tree
@@ -509,31 +478,3 @@ class GPTGenerator:
         out_ids[:, :T] = torch.where(padded, s["pad"], seq)
         out_lp[:, :T] = torch.where(padded, 0.0, slp)
         return _wrap(out_ids), _wrap(out_lp)
-
-    def _beam_graph_for(self, st, weights, s, ts0, required):
-        """_graph_for for the beam-search step: the warm-up step runs on a copy of the beam state"""
-        at = tuple(t.data_ptr() for group in weights for t in group)
-        if st.graph is not None and st.weights_at == at:
-            return st.graph
-        from ..ops import fallback
-        keep = [t.clone() for t in st.state()]
-        before = fallback.total()
-        self._beam_step(weights, st, s)   # warm-up: what it appends at the first step is rewritten by the first replay
-        clean = fallback.total() == before and os.environ.get("PHA_DECODE_ATTN", "1") != "0" \
-            and os.environ.get("PHA_BEAM_KERNEL", "1") != "0" \
-            and st.caches[0].dtype in (torch.bfloat16, torch.float16) and self.model.cfg.head_dim in (32, 64, 128)
-        for t, k in zip(st.state(), keep):
-            t.copy_(k)
-        if not clean and not required:
-            for c in st.caches:
-                c[:, torch.arange(c.shape[1], device=c.device), :, ts0.long()] = 0
-            return None
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            st.out = self._beam_step(weights, st, s)
-        self.captures += 1
-        for t, k in zip(st.state(), keep):   # capture launches nothing: the first replay is step 0
-            t.copy_(k)
-        st.graph, st.weights_at = g, at
-        return g

@@ -1388,6 +1388,15 @@ def _sample_max_v():
 SAMPLE_MAX_V = _sample_max_v()   # the kernel's vocabulary limit (0: library not built)
 
 
+def _row_vector_check(fn, name, t, dtype, n, dev, spelled=None):
+    """``t`` must be a contiguous ``dtype`` [n] tensor on ``dev``. ``spelled`` is the dtype as the message
+    names it: sample_logits has always said "float32" / "uint8" for ``u`` / ``finished`` where the other
+    messages print ``torch.int64`` and the like, and the tests' ``test_rejections`` match on the text."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,) or t.device != dev \
+            or not t.is_contiguous():
+        raise ValueError(f"{fn}: {name} must be a contiguous {spelled or dtype} [{n}] tensor on {dev}")
+
+
 def _sample_check(logits, u, temperature, top_k, top_p, finished, out_ids=None, out_logprob=None):
     """the argument errors of sample_logits, the same on every path (each names its argument)"""
     fn = "sample_logits"
@@ -1403,23 +1412,19 @@ def _sample_check(logits, u, temperature, top_k, top_p, finished, out_ids=None, 
     if logits.stride(1) != 1 or logits.stride(0) < V:
         raise ValueError(f"{fn}: logits strides {tuple(logits.stride())}: the last must be 1 and the first >= V={V}")
     dev = logits.device
-    if not isinstance(u, torch.Tensor) or u.dtype != torch.float32 or tuple(u.shape) != (B,) or u.device != dev \
-            or not u.is_contiguous():
-        raise ValueError(f"{fn}: u must be a contiguous float32 [{B}] tensor on {dev}")
+    _row_vector_check(fn, "u", u, torch.float32, B, dev, "float32")
     if not float(temperature) > 0.0:
         raise ValueError(f"{fn}: temperature={temperature} must be positive")
     if not (0.0 < float(top_p) <= 1.0):
         raise ValueError(f"{fn}: top_p={top_p} must be in (0, 1]")
     if int(top_k) != top_k or not (0 <= int(top_k) <= V):
         raise ValueError(f"{fn}: top_k={top_k} must be an integer in [0, V={V}]")
-    if finished is not None and (not isinstance(finished, torch.Tensor) or finished.dtype != torch.uint8
-                                 or tuple(finished.shape) != (B,) or finished.device != dev
-                                 or not finished.is_contiguous()):
-        raise ValueError(f"{fn}: finished must be a contiguous uint8 [{B}] tensor on {dev}")
-    for name, t, dt in (("out_ids", out_ids, torch.int64), ("out_logprob", out_logprob, torch.float32)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B,)
-                              or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"{fn}: {name} must be a contiguous {dt} [{B}] tensor on {dev}")
+    if finished is not None:
+        _row_vector_check(fn, "finished", finished, torch.uint8, B, dev, "uint8")
+    if out_ids is not None:
+        _row_vector_check(fn, "out_ids", out_ids, torch.int64, B, dev)
+    if out_logprob is not None:
+        _row_vector_check(fn, "out_logprob", out_logprob, torch.float32, B, dev)
 
 
 def _sample_reject(logits):
@@ -1576,11 +1581,9 @@ def _beam_check(logits, cum, finished, lengths, beam_size, cache_indirection, ti
             or R % beam_size:
         raise ValueError(f"{fn}: beam_size={beam_size!r} must be an int in [1, V={V}] that divides the {R} rows")
     dev = logits.device
-    for name, t, dt in (("cum", cum, torch.float32), ("finished", finished, torch.uint8),
-                        ("lengths", lengths, torch.int32)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (R,) or t.device != dev \
-                or not t.is_contiguous():
-            raise ValueError(f"{fn}: {name} must be a contiguous {dt} [{R}] tensor on {dev}")
+    _row_vector_check(fn, "cum", cum, torch.float32, R, dev)
+    _row_vector_check(fn, "finished", finished, torch.uint8, R, dev)
+    _row_vector_check(fn, "lengths", lengths, torch.int32, R, dev)
     t = cache_indirection
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != R or t.shape[1] < 1 \
             or t.device != dev or not t.is_contiguous():

@@ -84,6 +84,38 @@ def test_large_vocabulary_with_a_row_stride(dt):
     _check(case, want, got, d, f"V=50304 {dt}")
 
 
+@pytest.mark.parametrize("layout", ["V520", "V521_ld528", "V521_unaligned"])
+@pytest.mark.parametrize("dt", list(DTYPES))
+def test_a_one_beam_step_scores_as_the_greedy_sampler_bit_for_bit(dt, layout):
+    """Both kernels stage, key and score a row through csrc/kernels/logit_keys.h, so with one beam, cum = 0
+    and nothing finished the beam step must return the greedy sampler's token and, bitwise, its log
+    probability. The layouts reach every staging path: 16-byte loads only; 16-byte loads and a scalar
+    tail; a row base that is not 16-byte aligned, all scalar. Row 1 holds its maximum twice: the lower
+    index wins in both."""
+    from paddle_hackathon_amd.ops import hip
+    R, V, ld = (4, 520, 520) if layout == "V520" else (4, 521, 528)
+    off = 1 if layout == "V521_unaligned" else 0
+    buf = torch.zeros(off + R * ld, dtype=DTYPES[dt], device="cuda")
+    logits = buf[off:].view(R, ld)[:, :V]
+    logits.copy_(torch.randn(R, V, generator=torch.Generator().manual_seed(V + off)).to(DTYPES[dt]))
+    logits[1, 37] = logits[1, V - 1] = 9.0   # above every other logit of the row (a 520-sample normal)
+    assert (logits.data_ptr() % 16 == 0) == (off == 0) and logits.stride(0) == ld
+    assert int((logits[1] == logits[1].max()).sum()) == 2 and bool(torch.isfinite(logits).all())
+    cum = torch.zeros(R, dtype=torch.float32, device="cuda")
+    finished = torch.zeros(R, dtype=torch.uint8, device="cuda")
+    lengths = torch.zeros(R, dtype=torch.int32, device="cuda")
+    table = torch.zeros(R, 4, dtype=torch.int32, device="cuda")
+    assert hip.beam_search_step_supported(logits, cum, finished, lengths, 1, table, 0)
+    tok, parent, lp = hip.beam_search_step(logits, cum, finished, lengths, -1, 1, table, 0)
+    u = torch.zeros(R, dtype=torch.float32, device="cuda")
+    assert hip.sample_logits_supported(logits, u, top_k=1)
+    ids, slp = hip.sample_logits(logits, u, top_k=1)
+    assert torch.equal(tok, ids), f"{tok.tolist()} != {ids.tolist()}"
+    assert torch.equal(lp, slp), f"{lp.tolist()} != {slp.tolist()}"
+    assert int(tok[1]) == 37 and int(ids[1]) == 37
+    assert torch.equal(cum, lp) and int(parent.abs().sum()) == 0
+
+
 @pytest.mark.parametrize("form", ["int", "one_element"])
 def test_a_uniform_time_step_is_broadcast(form):
     from paddle_hackathon_amd.ops import hip
