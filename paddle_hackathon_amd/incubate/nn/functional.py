@@ -83,13 +83,46 @@ def _skinny_ok(x2, w, w_is_nk, bias=None, residual=None):
     return False
 
 
-def _skinny_linear(x, w, bias=None, act="none", residual=None):
+def _w8_ok(x2, wq, scale, bias=None, residual=None):
+    """_skinny_ok for the product from int8 weights, x2 [M, K] . wq[N, K]^T * scale (ops/hip.skinny_gemm_w8):
+    the same conditions and the same PHA_DECODE_GEMM=0; where it says no, the caller dequantises the
+    weight and runs today's path. At most 16 rows on the GPU with arguments the kernel cannot take is
+    recorded as a fallback; more rows or a CPU input is not one."""
+    if not (isinstance(x2, torch.Tensor) and x2.is_cuda and x2.dim() == 2 and isinstance(wq, torch.Tensor)
+            and wq.dim() == 2):
+        return False
+    if x2.shape[0] > _ops.hip.SKINNY_GEMM_MAX_M or x2.shape[0] < 1:
+        return False
+    if os.environ.get("PHA_DECODE_GEMM", "1") == "0" or not _ops.fused._use_hip(x2):
+        return False
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x2, bias, residual)):
+        return False
+    if _ops.hip.skinny_gemm_w8_supported(x2, wq, scale, bias, residual):
+        return True
+    from ...ops import fallback
+    fallback.note("decode_gemm_w8", f"{_ops.hip.skinny_gemm_w8_why_not(x2, wq, scale, bias, residual)} -> "
+                                    "dequantised weight on the bf16 / fp16 path")
+    return False
+
+
+def _w8_dequant(wq, scale, dtype):
+    """int8 [N, K] with its fp32 per-channel scale -> the [K, N] weight in ``dtype`` that today's paths take
+    (what nn.quant.weight_dequantize returns): a temporary, made where the int8 kernel does not run"""
+    return (wq.to(torch.float32) * scale.to(torch.float32).reshape(-1, 1)).to(dtype).t().contiguous()
+
+
+def _skinny_linear(x, w, bias=None, act="none", residual=None, scale=None):
     """act(x . w + bias) + residual for x [..., K] of at most 16 rows and w [K, N] on the
-    weight-streaming kernels, or None where _skinny_ok keeps the product on today's path"""
+    weight-streaming kernels, or None where _skinny_ok keeps the product on today's path. With
+    ``scale`` (fp32 [N]) ``w`` is int8 [N, K] and the product runs on the int8 kernel, or None."""
     x2 = x.reshape(-1, x.shape[-1])
     r2 = None if residual is None else residual.reshape(-1, residual.shape[-1])
     if r2 is not None and not r2.is_contiguous():
         r2 = r2.contiguous()   # e.g. one token sliced out of a [B, T, E] input: at most 16 rows to copy
+    if scale is not None:
+        if not _w8_ok(x2, w, scale, bias, r2):
+            return None
+        return _ops.hip.skinny_gemm_w8(x2, w, scale, bias, act, r2).reshape(*x.shape[:-1], w.shape[0])
     if not _skinny_ok(x2, w, False, bias, r2):
         return None
     return _ops.hip.skinny_gemm(x2, w, False, bias, act, r2).reshape(*x.shape[:-1], w.shape[-1])
@@ -314,7 +347,9 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                             ffn_ln_scales, ffn_ln_biases, ffn1_weights, ffn1_biases, ffn2_weights, ffn2_biases,
                             pre_layer_norm=True, epsilon=1e-05, cache_kvs=None, time_step=None, attn_mask=None,
                             dropout_rate=0.0, activation="gelu", training=False, mode="upscale_in_train",
-                            trans_qkvw=True, ring_id=-1, name=None, cache_indirection=None, beam_size=1):
+                            trans_qkvw=True, ring_id=-1, name=None, cache_indirection=None, beam_size=1,
+                            qkv_weight_scales=None, linear_weight_scales=None, ffn1_weight_scales=None,
+                            ffn2_weight_scales=None):
     """Stack of pre-LN decoder layers for generation. ``cache_kvs[i]`` is a preallocated
     [2, B, H, max_seq, D] buffer updated in place: context stage (time_step None) writes
     positions [0, S); decode stage (S == 1) writes position ``time_step`` and attends over
@@ -340,9 +375,24 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     layer's cache, while the new key and value go to row b's own cache row. The kernel pair takes the
     table as it is (``ops.hip.decode_attention``); the composite gathers each row's keys and values
     through it into a temporary, without a host sync on the GPU. A scalar ``time_step`` is broadcast
-    to the B rows."""
+    to the B rows.
+
+    Weight-only int8: ``qkv_weight_scales``, ``linear_weight_scales``, ``ffn1_weight_scales`` and
+    ``ffn2_weight_scales`` (all four or none) are lists of fp32 per-output-channel scales, and the four
+    weight lists then hold int8 ``[N, K]`` tensors as ``nn.quant.weight_quantize`` returns them (QKV
+    ``[3, H, D, E]`` with scales ``[3 * H * D]``; ``trans_qkvw=False`` is a ``ValueError``). With at most 16
+    rows on the GPU every product runs on the int8 weight-streaming kernel (csrc/kernels/skinny_w8.hip),
+    bias / activation / residual fused as above; in the context stage and on the CPU the weight is
+    dequantised to the input's dtype, one temporary at a time, and the product runs as it does today."""
     h = _u(x)
     B, S, E = h.shape
+    w8 = (qkv_weight_scales, linear_weight_scales, ffn1_weight_scales, ffn2_weight_scales)
+    if any(s is not None for s in w8) and any(s is None for s in w8):
+        raise ValueError("fused_multi_transformer: give all four of qkv_weight_scales, linear_weight_scales, "
+                         "ffn1_weight_scales and ffn2_weight_scales (int8 weights) or none of them")
+    w8 = w8[0] is not None
+    if w8 and not trans_qkvw:
+        raise ValueError("fused_multi_transformer: int8 weights need trans_qkvw=True (qkv_weights [3, H, D, E])")
     ts = ts_dev = ts_rows = None
     if time_step is not None:
         t = _u(time_step)
@@ -383,6 +433,19 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     # (dropout an identity: rate 0, or inference in the upscale-in-train mode; no all-reduce)
     epi = skinny and ring_id < 0 and (dropout_rate == 0 or
                                       (not training and mode in ("upscale_in_train", "upscale-in-train")))
+
+    def product(x, w, scale, bias, act="none", res=None):
+        """(act(x . w + bias) + res on a weight-streaming kernel or None, the [K, N] weight of today's path)"""
+        fuse = skinny and act in _ops.hip._SKINNY_ACT
+        out = _skinny_linear(x, w, bias, act, res, scale) if fuse else None
+        if out is None and scale is not None:
+            w = _w8_dequant(w, scale, x.dtype)
+            out = _skinny_linear(x, w, bias, act, res) if fuse else None
+        return out, w
+
+    def scale_of(scales, i):
+        return _u(scales[i]).reshape(-1) if w8 else None
+
     for i in range(len(qkv_weights)):
         residual = h
         a = _ln(h, _u(ln_scales[i]), _u(ln_biases[i]), epsilon) if pre_layer_norm else h
@@ -395,7 +458,10 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             w2 = w.reshape(E, 3 * H * D)
         a2 = a.reshape(B * S, E)
         qb = _u(qkv_biases[i]) if qkv_biases is not None and qkv_biases[i] is not None else None
-        if skinny and _skinny_ok(a2, w2, trans_qkvw):
+        tq, qs = trans_qkvw, scale_of(qkv_weight_scales, i)
+        if qs is not None and not (skinny and _w8_ok(a2, w2, qs)):
+            w2, tq, qs = _w8_dequant(w2, qs, a2.dtype), False, None
+        if qs is not None or (skinny and _skinny_ok(a2, w2, tq)):
             # nothing here needs a gradient, so a stand-in of the product's shape and dtype picks the
             # attention path first: the decode kernels add the QKV bias themselves, anywhere else it
             # goes into this product's epilogue
@@ -403,13 +469,14 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                                                       ts_dev if ts_dev is not None else False, dropout_rate,
                                                       training, ind, beam_size)
             qbe = None if use_decode or qb is None else qb.reshape(-1)
-            if qbe is not None and not _ops.hip.skinny_gemm_supported(a2, w2, trans_qkvw, qbe):
+            if qbe is not None and not (_ops.hip.skinny_gemm_supported(a2, w2, tq, qbe) if qs is None else
+                                        _ops.hip.skinny_gemm_w8_supported(a2, w2, qs, qbe)):
                 qbe = None   # added below as today
-            qkv = _ops.hip.skinny_gemm(a2, w2, trans_qkvw, qbe)
+            qkv = _ops.hip.skinny_gemm(a2, w2, tq, qbe) if qs is None else _ops.hip.skinny_gemm_w8(a2, w2, qs, qbe)
             if qbe is not None:
                 qb = None
         else:
-            qkv = a2 @ (w2.t() if trans_qkvw else w2)
+            qkv = a2 @ (w2.t() if tq else w2)
             use_decode = decode and _decode_kernel_ok(qkv.reshape(B, 3, H, D), _u(cache_kvs[i]), mask,
                                                       ts_dev if ts_dev is not None else False, dropout_rate, training,
                                                       ind, beam_size)
@@ -454,7 +521,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                 o = _attention(q, k, v, m, dropout_rate, training, mode, causal=causal and S > 1)
             o = o.transpose(1, 2).reshape(B, S, H * D)
         lw, lb = _u(linear_weights[i]), _u(linear_biases[i]) if linear_biases is not None else None
-        o2 = _skinny_linear(o, lw, lb, "none", residual if epi else None) if skinny else None
+        o2, lw = product(o, lw, scale_of(linear_weight_scales, i), lb, "none", residual if epi else None)
         if o2 is not None and epi:
             h = o2
         else:
@@ -467,10 +534,11 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         residual = h
         f = _ln(h, _u(ffn_ln_scales[i]), _u(ffn_ln_biases[i]), epsilon) if pre_layer_norm else h
         w1, b1 = _u(ffn1_weights[i]), _u(ffn1_biases[i]) if ffn1_biases is not None else None
-        f1 = _skinny_linear(f, w1, b1, activation) if skinny and activation in ("gelu", "gelu_tanh", "relu") else None
+        f1, w1 = product(f, w1, scale_of(ffn1_weight_scales, i), b1,
+                         activation if activation in ("gelu", "gelu_tanh", "relu") else None)
         f = f1 if f1 is not None else _act(f @ w1, b1, activation)
         w2f, b2 = _u(ffn2_weights[i]), _u(ffn2_biases[i]) if ffn2_biases is not None else None
-        f2 = _skinny_linear(f, w2f, b2, "none", residual if epi else None) if skinny else None
+        f2, w2f = product(f, w2f, scale_of(ffn2_weight_scales, i), b2, "none", residual if epi else None)
         if f2 is not None and epi:
             h = f2
         else:

@@ -32,6 +32,14 @@ ordered (head, 3, D) while the decode kernels need (3, head, D): the generator k
 copy of each layer's QKV weight (``[E, 3, H, D]``, passed with ``trans_qkvw=False``) and bias, and
 refreshes it in place when the parameter's version counter changes. At GPT-3 1.3B that copy is
 25 MB per layer (600 MB for the 24 layers in bf16).
+
+``weight_only="int8"`` runs the four products of every layer from int8 copies of their weights
+(``nn.quant.weight_quantize``: symmetric, one fp32 scale per output channel, ``[N, K]``), kept on the
+generator per layer and refreshed like the QKV copy; QKV is quantised from the repacked (3, head, D)
+order and takes the place of the bf16 copy. The decode step streams them through the int8
+weight-streaming kernel (csrc/kernels/skinny_w8.hip), half the bytes per token; the prefill runs on the
+same weights dequantised, so the prompt and the continuation see one model. The embedding and the LM
+head stay as they are.
 """
 from __future__ import annotations
 
@@ -85,8 +93,10 @@ class GPTGenerator:
     def __init__(self, model):
         self.model = model
         self._qkv = {}        # layer index -> (weight version, bias version, repacked weight, repacked bias)
-        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged) -> _State;
-        #                       (B, cache length, "beam_search", num_beams, eos) -> _State
+        self._w8 = {}         # layer index -> (parameter versions, [qkv q, scale, out q, scale, f1 q, scale, f2 q, scale,
+        #                       repacked qkv bias]): the int8 copies of weight_only="int8"
+        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged, weight_only)
+        #                       -> _State; (B, cache length, "beam_search", num_beams, eos, weight_only) -> _State
         self._eager = set()   # keys whose warm-up step left the kernel path: not tried again
         self.captures = 0     # hipGraph captures so far (a second generate call adds none)
         self.last_caches = None
@@ -94,18 +104,60 @@ class GPTGenerator:
 
     def clear(self):
         """drop the captured graphs with their static buffers (each key holds its own KV caches) and
-        the repacked QKV copies; the next call builds what it needs again"""
+        the repacked QKV copies and int8 weights; the next call builds what it needs again"""
         self._graphs.clear()
         self._eager.clear()
         self._qkv.clear()
+        self._w8.clear()
 
     # ------------------------------------------------------------------------------ weights
-    def _layer_weights(self):
+    def _int8_layer(self, i, layer):
+        """layer i's int8 copies: [qkv q [3, H, D, E], scale, out q [N, K], scale, f1 q, scale, f2 q, scale,
+        qkv bias (3, H, D)], requantised in place (a captured graph reads them) when a parameter's version
+        counter moved"""
+        from ..nn.quant import weight_quantize
+        cfg = self.model.cfg
+        H, D, E = cfg.num_heads, cfg.head_dim, cfg.hidden_size
+        qw, qb = layer.self_attn.qkv_proj.weight._t, layer.self_attn.qkv_proj.bias._t
+        mats = (qw, layer.self_attn.out_proj.weight._t, layer.mlp.linear1.weight._t, layer.mlp.linear2.weight._t)
+        ver = tuple(t._version for t in mats + (qb,))
+        ent = self._w8.get(i)
+        if ent is not None and ent[0] == ver and ent[1][0].device == qw.device and ent[1][8].dtype == qb.dtype:
+            return ent[1]
+        new = []
+        for j, m in enumerate(mats):
+            m = m.detach()
+            q, sc = weight_quantize(m.view(E, H, 3, D).permute(0, 2, 1, 3).reshape(E, 3 * H * D) if j == 0 else m)
+            new += [q._t.view(3, H, D, E) if j == 0 else q._t, sc._t]
+        new.append(qb.detach().view(H, 3, D).permute(1, 0, 2).contiguous())
+        if ent is not None and all(a.shape == b.shape and a.dtype == b.dtype and a.device == b.device
+                                   for a, b in zip(ent[1], new)):
+            for a, b in zip(ent[1], new):
+                a.copy_(b)
+            new = ent[1]
+        self._w8[i] = (ver, new)
+        return new
+
+    def _layer_weights(self, weight_only=None):
+        """the twelve per-layer lists fused_multi_transformer takes, followed with ``weight_only`` by the four
+        lists of scales (the four weight lists then hold the int8 copies)"""
         cfg = self.model.cfg
         H, D, E = cfg.num_heads, cfg.head_dim, cfg.hidden_size
         names = ("ln_s", "ln_b", "qkv_w", "qkv_b", "out_w", "out_b", "fln_s", "fln_b", "f1_w", "f1_b", "f2_w", "f2_b")
+        if weight_only:
+            names += ("qkv_s", "out_s", "f1_s", "f2_s")
         w = {k: [] for k in names}
         for i, layer in enumerate(self.model.gpt.layers):
+            if weight_only:
+                c = self._int8_layer(i, layer)
+                for k, t in zip(("qkv_w", "qkv_s", "out_w", "out_s", "f1_w", "f1_s", "f2_w", "f2_s", "qkv_b"), c):
+                    w[k].append(t)
+                for k, t in (("ln_s", layer.norm1.weight), ("ln_b", layer.norm1.bias),
+                             ("out_b", layer.self_attn.out_proj.bias), ("fln_s", layer.norm2.weight),
+                             ("fln_b", layer.norm2.bias), ("f1_b", layer.mlp.linear1.bias),
+                             ("f2_b", layer.mlp.linear2.bias)):
+                    w[k].append(t._t)
+                continue
             qw, qb = layer.self_attn.qkv_proj.weight._t, layer.self_attn.qkv_proj.bias._t
             ent = self._qkv.get(i)
             if ent is None or ent[2].dtype != qw.dtype or ent[2].device != qw.device:
@@ -132,9 +184,12 @@ class GPTGenerator:
 
     def _stack(self, x, weights, caches, time_step=None, **beam):
         from ..incubate.nn import functional as FF
-        out, _ = FF.fused_multi_transformer(x, *weights, pre_layer_norm=True, epsilon=self.model.cfg.layer_norm_eps,
-                                            cache_kvs=caches, time_step=time_step, activation="gelu_tanh",
-                                            trans_qkvw=False, **beam)
+        scales = dict(zip(("qkv_weight_scales", "linear_weight_scales", "ffn1_weight_scales", "ffn2_weight_scales"),
+                          weights[12:]))   # int8 weights: QKV [3, H, D, E], the trans_qkvw layout
+        out, _ = FF.fused_multi_transformer(x, *weights[:12], pre_layer_norm=True,
+                                            epsilon=self.model.cfg.layer_norm_eps, cache_kvs=caches,
+                                            time_step=time_step, activation="gelu_tanh", trans_qkvw=bool(scales),
+                                            **scales, **beam)
         return out._t
 
     def _logits(self, h):
@@ -216,7 +271,7 @@ class GPTGenerator:
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, decode_strategy="greedy_search", temperature=1.0, top_k=0, top_p=1.0,
                  eos_token_id=None, pad_token_id=0, seed=None, use_graph=None, seq_lens=None, attention_mask=None,
-                 num_beams=None, num_return_sequences=1, length_penalty=0.0):
+                 num_beams=None, num_return_sequences=1, length_penalty=0.0, weight_only=None):
         """``max_new_tokens`` tokens after ``input_ids`` [B, prompt]: (ids int64 [B, max_new_tokens],
         scores fp32 [B, max_new_tokens]), the score being the log probability of the token under the
         temperature-scaled, unfiltered softmax (0 at padded positions).
@@ -251,9 +306,18 @@ class GPTGenerator:
         shape, the log probability of each token along the beam's own history (0 at padded
         positions), so a row of scores sums to the beam's score. ``num_beams=1`` is greedy search, bit
         for bit. The step runs R = B * K rows; up to 16 rows it stays on the kernels and is captured
-        like the other strategies (the graph is kept per (B, cache length, num_beams, eos)), above
+        like the other strategies (the graph is kept per (B, cache length, num_beams, eos, weight_only)), above
         that it runs eagerly on the composites and library GEMMs (recorded as fallbacks). The prompt
         is prefilled once per item, not once per beam.
+
+        ``weight_only`` "int8" runs the four products of every layer (QKV, output projection, ffn1, ffn2)
+        from int8 copies of their weights with one fp32 scale per output channel
+        (``nn.quant.weight_quantize``), in the prefill and in every decode step alike: the result is that
+        of the model with those four matrices per layer replaced by their dequantised values. The decode
+        step streams the int8 weights through ``ops.hip.skinny_gemm_w8``. The copies are kept on the
+        generator, refreshed when a parameter changes and dropped by ``clear()``; the model's parameters
+        are untouched, and the embedding and the LM head stay in the model's dtype. The mode is part of
+        every graph key. Any other value is a ``ValueError``.
 
         The model must be in eval mode with ``tensor_parallel_degree == 1``, and
         ``longest prompt + max_new_tokens <= max_position_embeddings``.
@@ -261,7 +325,7 @@ class GPTGenerator:
         ``use_graph`` None captures the decode step in one hipGraph when the model is on the GPU and
         a warm-up step took the kernel path everywhere (no recorded fallback, device-side time step);
         True insists on it, False runs the same step eagerly. The graph and its static buffers are kept
-        on the generator per (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged), KV
+        on the generator per (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged, weight_only), KV
         caches included; ``GPTGenerator.clear()`` releases them. The prompt lengths are data of the
         ragged graph, not part of its key: one capture serves every mix of lengths with the same
         longest prompt."""
@@ -272,6 +336,8 @@ class GPTGenerator:
             raise RuntimeError("generate: the model is in training mode; call model.eval() first")
         if decode_strategy not in STRATEGIES:
             raise ValueError(f"generate: decode_strategy must be one of {STRATEGIES}, got {decode_strategy!r}")
+        if weight_only not in (None, "int8"):
+            raise ValueError(f"generate: weight_only={weight_only!r}: None or 'int8' (the only weight-only type there is)")
         beam = decode_strategy == "beam_search"
         if num_beams is None:
             if beam:   # there is no default width: the cost of a call is B * num_beams rows per step
@@ -313,9 +379,10 @@ class GPTGenerator:
             if num_beams > cfg.vocab_size:
                 raise ValueError(f"generate: num_beams={num_beams} exceeds the vocabulary ({cfg.vocab_size})")
             s.update(beams=num_beams, nret=num_return_sequences, length_penalty=float(length_penalty))
-            return self._generate_beam(ids_in, lens, n_new, s, use_graph)
-        key = (B, cache_len, s["strategy"], s["temperature"], s["top_k"], s["top_p"], s["eos"], s["pad"], ragged)
-        weights = self._layer_weights()
+            return self._generate_beam(ids_in, lens, n_new, s, use_graph, weight_only)
+        key = (B, cache_len, s["strategy"], s["temperature"], s["top_k"], s["top_p"], s["eos"], s["pad"], ragged,
+               weight_only)
+        weights = self._layer_weights(weight_only)
         st, want_graph = self._state_for(key, B, cache_len, ragged, False, use_graph, n_new)
 
         # uniforms of every step, drawn up front (no per-step generator state in a captured graph)
@@ -425,15 +492,15 @@ class GPTGenerator:
         return g
 
     # ------------------------------------------------------------------------------ beam search
-    def _generate_beam(self, ids_in, lens, n_new, s, use_graph):
+    def _generate_beam(self, ids_in, lens, n_new, s, use_graph, weight_only=None):
         """generate()'s beam-search branch: ``ids_in`` [B, P] on the device, ``lens`` the prompt
         lengths or None"""
         model, dev = self.model, ids_in.device
         B, P = ids_in.shape
         K, eos = s["beams"], s["eos"]
         R, cache_len = B * K, P + n_new
-        key = (B, cache_len, "beam_search", K, eos)
-        weights = self._layer_weights()
+        key = (B, cache_len, "beam_search", K, eos, weight_only)
+        weights = self._layer_weights(weight_only)
         st, want_graph = self._state_for(key, R, cache_len, True, True, use_graph, n_new)
         # per group: beam 0 starts at 0, the others at -inf, so the first step's K picks all continue beam 0
         st.cum.copy_(torch.tensor([0.0] + [float("-inf")] * (K - 1), dtype=torch.float32).repeat(B))

@@ -134,6 +134,10 @@ SIGNATURES = {
     "pha_skinny_gemm_tile": (I, [I, P, P]),
     "pha_skinny_gemm_plan": (I, [I, I, I, P, P]),
     "pha_skinny_gemm": (I, [I, I, P, LG, P, P, P, P, P, I, I, I, I, I, I, P]),
+    # skinny_w8.hip
+    "pha_skinny_w8_tile": (I, [P, P]),
+    "pha_skinny_w8_plan": (I, [I, I, P, P]),
+    "pha_skinny_gemm_w8": (I, [I, P, LG, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     # split.hip
     "pha_split3_f32": (I, [P, P, LG, LG, I, P]),
 }

@@ -1376,6 +1376,117 @@ def skinny_gemm(x, w, w_is_nk, bias=None, act="none", residual=None, nsplit=None
 
 
 # ----------------------------------------------------------------------------
+# weight-only int8 weight-streaming GEMM for M <= 16 rows (csrc/kernels/skinny_w8.hip)
+# ----------------------------------------------------------------------------
+def skinny_gemm_w8_tile():
+    """(column tile, K step) of the int8 kernel; a split is a multiple of the K step"""
+    bn, ks = c_int(0), c_int(0)
+    _check(_L().pha_skinny_w8_tile(ctypes.byref(bn), ctypes.byref(ks)), "skinny_gemm_w8_tile")
+    return bn.value, ks.value
+
+
+def skinny_gemm_w8_plan(N, K):
+    """(nsplit, k_per_split) the int8 kernel uses for an [M, K] x [N, K]^T product: a function of N and K
+    alone (never M or data), so a captured graph stays valid and results reproduce"""
+    L = _L()
+    ns, kps = c_int(0), c_int(0)
+    if int(N) < 1 or int(K) < 1:
+        raise ValueError(f"skinny_gemm_w8_plan: N={N} K={K} must be positive")
+    _check(L.pha_skinny_w8_plan(int(N), int(K), ctypes.byref(ns), ctypes.byref(kps)), "skinny_gemm_w8_plan")
+    return ns.value, kps.value
+
+
+def _skinny_w8_reject(x, wq, scale, bias, residual):
+    """why skinny_gemm_w8 cannot take these arguments (names the argument), or None"""
+    if not (isinstance(x, torch.Tensor) and isinstance(wq, torch.Tensor) and isinstance(scale, torch.Tensor)):
+        return "x, wq and scale must be tensors"
+    if not x.is_cuda:
+        return f"x is on {x.device}, not a GPU"
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        return f"x is {x.dtype}; the kernel takes bfloat16 or float16"
+    dev, dt = x.device, x.dtype
+    if x.dim() != 2:
+        return f"x must be 2-D, got {tuple(x.shape)}"
+    if wq.dim() != 2:
+        return f"wq must be 2-D, got {tuple(wq.shape)}"
+    M, K = x.shape
+    if M < 1 or M > SKINNY_GEMM_MAX_M:
+        return f"x has M={M} rows; the kernel takes 1 to {SKINNY_GEMM_MAX_M}"
+    N = wq.shape[0]
+    if wq.shape[1] != K:
+        return f"wq {tuple(wq.shape)} must be [N, K] with x's K={K}"
+    if K % 16 or N % 8 or K < 16 or N < 8:
+        return f"K={K} must be a positive multiple of 16 and N={N} one of 8"
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.stride(0) < K:
+        return f"x strides {tuple(x.stride())}: the last must be 1 and the first a multiple of 8 that is >= K"
+    for name, t, tdt, shape in (("wq", wq, torch.int8, (N, K)), ("scale", scale, torch.float32, (N,)),
+                                ("bias", bias, dt, (N,)), ("residual", residual, dt, (M, N))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != tdt:
+            return f"{name} must be a {tdt} tensor on {dev}"
+        if tuple(t.shape) != shape:
+            return f"{name} must have shape {shape}, got {tuple(t.shape)}"
+        if not t.is_contiguous():
+            return f"{name} is not contiguous"
+    for name, t in (("x", x), ("wq", wq), ("bias", bias), ("residual", residual)):
+        if t is not None and t.data_ptr() % 16:
+            return f"{name} is not 16-byte aligned"
+    return None
+
+
+def skinny_gemm_w8_supported(x, wq, scale, bias=None, residual=None):
+    """what skinny_gemm_w8 takes: x bf16 / fp16 [M, K] on a GPU with 1 <= M <= 16, unit inner stride and a
+    row stride that is a multiple of 8; a contiguous int8 wq [N, K] and fp32 scale [N]; K a multiple of
+    16 and N of 8; contiguous bias [N] and residual [M, N] of x's dtype; x, wq, bias and residual
+    16-byte aligned; everything on x's device"""
+    return _lib.lib is not None and _skinny_w8_reject(x, wq, scale, bias, residual) is None
+
+
+def skinny_gemm_w8_why_not(x, wq, scale, bias=None, residual=None):
+    """the reason skinny_gemm_w8 would reject these arguments, for the fallback log"""
+    if _lib.lib is None:
+        return "kernel library not loaded"
+    return _skinny_w8_reject(x, wq, scale, bias, residual) or "supported"
+
+
+def skinny_gemm_w8(x, wq, scale, bias=None, act="none", residual=None, nsplit=None, out=None):
+    """out[M, N] = act((x[M, K] @ wq[N, K]^T) * scale[N] + bias) + residual from int8 weights on the
+    weight-streaming kernel, M <= 16: the weights are dequantised exactly in registers, the sum is fp32,
+    the per-channel fp32 ``scale`` multiplies it and the result is rounded once. ``act`` is "none",
+    "gelu" (erf), "gelu_tanh" or "relu". ``nsplit`` None takes skinny_gemm_w8_plan's deterministic
+    split; an explicit value splits K evenly (in multiples of 16) and must leave no split empty.
+    ``out``, if given, is a contiguous, 16-byte aligned [M, N] tensor of x's dtype on x's device."""
+    fn = "skinny_gemm_w8"
+    why = _skinny_w8_reject(x, wq, scale, bias, residual)
+    if why is not None:
+        raise ValueError(f"{fn}: {why}")
+    if act not in _SKINNY_ACT:
+        raise ValueError(f"{fn}: act must be one of {sorted(_SKINNY_ACT)}, got {act!r}")
+    L = _L()
+    M, K = x.shape
+    N = wq.shape[0]
+    if nsplit is None:
+        ns, kps = skinny_gemm_w8_plan(N, K)
+    else:
+        ns = int(nsplit)
+        if ns < 1:
+            raise ValueError(f"{fn}: nsplit={nsplit} must be at least 1")
+        kps = -(-(-(-K // ns)) // 16) * 16
+        if (ns - 1) * kps >= K:
+            raise ValueError(f"{fn}: nsplit={ns} leaves a split empty at K={K} (k_per_split={kps})")
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != x.dtype or out.device != x.device \
+            or tuple(out.shape) != (M, N) or not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError(f"{fn}: out must be a contiguous, 16-byte aligned {x.dtype} [{M}, {N}] tensor on {x.device}")
+    ws = torch.empty((ns, M, N), dtype=torch.float32, device=x.device) if ns > 1 else None
+    _check(L.pha_skinny_gemm_w8(_DT[x.dtype], _ptr(x), x.stride(0), _ptr(wq), _ptr(scale), _ptr(bias), _ptr(residual),
+                                _ptr(out), _ptr(ws), M, N, K, ns, kps, _SKINNY_ACT[act], _stream(x)), fn)
+    return out
+
+
+# ----------------------------------------------------------------------------
 # next-token sampling (csrc/kernels/sampling.hip)
 # ----------------------------------------------------------------------------
 SAMPLE_MAX_B = 16   # rows per call: the decode step's batch, as SKINNY_GEMM_MAX_M

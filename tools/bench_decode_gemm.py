@@ -7,13 +7,15 @@ against the library calls that PHA_DECODE_GEMM=0 keeps.
     Infinity Cache. Arms: the kernel with its epilogue; the library call it replaces; the library
     call plus the elementwise passes the epilogue absorbs (bias + GELU, residual add), as
     fused_multi_transformer runs them. The arms alternate in one process; medians over the rounds.
+    With --w8 part (b) is instead the int8 kernel (csrc/kernels/skinny_w8.hip, weights int8 [N, K] with a
+    scale per channel) against the bf16 kernel of this tree on the same shapes, same method.
 (c) one decode step of the 24-layer model of tools/bench_decode_attn.py part (b), PHA_DECODE_GEMM=0
     against 1, eager (device time step) and replayed from a captured graph, alternating.
 
 --profile-step N replays the captured step N times and exits (for a kernel trace of one arm; the
 switch is taken from the environment).
 
-Prints markdown tables. Usage: python tools/bench_decode_gemm.py [--rounds 7] [--iters 40] [--skip-model]
+Prints markdown tables. Usage: python tools/bench_decode_gemm.py [--rounds 7] [--iters 40] [--skip-model] [--w8]
 """
 import argparse
 import os
@@ -122,6 +124,48 @@ def bench_products(rounds, iters):
     print()
 
 
+def bench_products_w8(rounds, iters):
+    gen = torch.Generator(device="cuda").manual_seed(0)
+
+    def r(*shape, s=1.0):
+        return (torch.randn(*shape, device="cuda", generator=gen) * s).bfloat16()
+
+    # name, M, N, K, layout of the bf16 arm, bias in the epilogue, activation, residual
+    cases = [("qkv [N,K]", 8, 3 * E, E, True, False, "none", False),
+             ("qkv [K,N]", 8, 3 * E, E, False, False, "none", False),
+             ("out proj", 8, E, E, False, True, "none", True),
+             ("ffn1 + GELU", 8, DFF, E, False, True, "gelu", False),
+             ("ffn2", 8, E, DFF, False, True, "none", True),
+             ("out proj", 1, E, E, False, True, "none", True),
+             ("out proj", 16, E, E, False, True, "none", True)]
+    print(f"### (b, --w8) per product, int8 weights against bf16 weights, {LAYERS} weight buffers in turn inside one "
+          f"graph, us per call, median of {rounds} rounds x {iters} replays (min - max)\n")
+    print("| product (bf16 layout) | M | N | K | int8 nsplit x k | bf16 nsplit x k | int8 kernel | bf16 kernel | speedup | "
+          "int8 bytes | int8 TB/s | bf16 TB/s | wins |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+
+    def us(t):
+        return f"{t[0] * 1e3 / LAYERS:.2f} ({t[1] * 1e3 / LAYERS:.2f} - {t[2] * 1e3 / LAYERS:.2f})"
+
+    for name, M, N, K, nk, has_bias, act, has_res in cases:
+        ws = [r(N, K, s=K ** -0.5) if nk else r(K, N, s=K ** -0.5) for _ in range(LAYERS)]
+        qs = [torch.randint(-128, 128, (N, K), device="cuda", generator=gen, dtype=torch.int8) for _ in range(LAYERS)]
+        sc = torch.rand(N, device="cuda", generator=gen) * (K ** -0.5 / 74)
+        x, bias, res = r(M, K), (r(N) if has_bias else None), (r(M, N) if has_res else None)
+        graphs = [capture(lambda i: hip.skinny_gemm_w8(x, qs[i], sc, bias, act, res)),
+                  capture(lambda i: hip.skinny_gemm(x, ws[i], nk, bias, act, res))]
+        t8, t16 = alternate([lambda _, g=g: g.replay() for g in graphs], iters, rounds)
+        tb8 = N * K / (t8[0] / LAYERS * 1e-3) / 1e12
+        tb16 = N * K * 2 / (t16[0] / LAYERS * 1e-3) / 1e12
+        wins = "yes" if t16[0] - t8[0] > max(t8[2] - t8[1], t16[2] - t16[1]) else "no"
+        p8, p16 = hip.skinny_gemm_w8_plan(N, K), hip.skinny_gemm_plan(N, K, nk)
+        print(f"| {name} | {M} | {N} | {K} | {p8[0]} x {p8[1]} | {p16[0]} x {p16[1]} | {us(t8)} | {us(t16)} | "
+              f"{t16[0] / t8[0]:.2f}x | {N * K / 1e6:.1f} MB | {tb8:.2f} | {tb16:.2f} | {wins} |")
+        del graphs, ws, qs
+        torch.cuda.empty_cache()
+    print()
+
+
 def model_step():
     ts = 1023
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -189,6 +233,7 @@ def main():
     ap.add_argument("--iters", type=int, default=40)
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--skip-products", action="store_true")
+    ap.add_argument("--w8", action="store_true", help="part (b): the int8 kernel against the bf16 kernel")
     ap.add_argument("--profile-step", type=int, default=0)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -205,7 +250,7 @@ def main():
     print(f"device: {torch.cuda.get_device_name(0)}\n")
     with torch.no_grad():
         if not a.skip_products:
-            bench_products(a.rounds, a.iters)
+            (bench_products_w8 if a.w8 else bench_products)(a.rounds, a.iters)
         if not a.skip_model:
             bench_model(a.rounds, a.iters)
 

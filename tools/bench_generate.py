@@ -9,6 +9,9 @@
     search and once sampling with top-k 50 + top-p 0.9: replayed from the captured graph and eager, each
     with PHA_SAMPLE_KERNEL=0 and 1; tokens/s and ms per token over the whole call (prefill included).
 
+    With --w8 part (c) is instead greedy search replayed from the graph and eager, each with
+    weight_only=None and weight_only="int8" (the four products of every layer from int8 weights).
+
 (d) with --ragged: the same model, B = 8, 128 new tokens, greedy, replayed from the graph: prompts of
     16..128 tokens (``seq_lens``, a time step per row) against all eight at 128.
 
@@ -23,7 +26,7 @@ profiles/decode_gemm/README.md: the kernel's median is below the other arm's by 
 min - max spread of the two.
 
 Prints markdown tables. Usage: python tools/bench_generate.py [--rounds 7] [--iters 20] [--skip-model] [--ragged]
-                                                     [--beams 4]
+                                                     [--beams 4] [--w8]
 """
 import argparse
 import os
@@ -166,6 +169,44 @@ def _generate_arms(gens, ids, new, rounds, what, kw, B, prompt):
     print(f"\nthe four arms return {'the same' if same else 'different'} tokens\n")
 
 
+def bench_generate_w8(rounds, B=8, prompt=128, new=128):
+    import paddle_hackathon_amd as paddle
+    from paddle_hackathon_amd.models import GPTForPretraining, GPTGenerator, gpt_config
+    paddle.set_device("gpu:0")
+    paddle.seed(0)
+    model = paddle.amp.decorate(GPTForPretraining(gpt_config("gpt3-1.3b")), level="O2", dtype="bfloat16")
+    model.eval()
+    ids = torch.randint(0, V, (B, prompt), device="cuda", generator=torch.Generator(device="cuda").manual_seed(2))
+    gen = GPTGenerator(model)
+
+    def arm(mode, graph):
+        def fn():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out, _ = gen.generate(ids, new, use_graph=graph, weight_only=mode)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, out._t
+        return fn
+
+    arms = [("graph, bf16 weights", arm(None, True)), ("graph, weight_only=\"int8\"", arm("int8", True)),
+            ("eager, bf16 weights", arm(None, False)), ("eager, weight_only=\"int8\"", arm("int8", False))]
+    outs = [fn()[1] for _, fn in arms]   # warm-up: quantises the weights, captures the graphs
+    samples = [[] for _ in arms]
+    for _ in range(rounds):
+        for s, (_, fn) in zip(samples, arms):
+            s.append(fn()[0])
+    print(f"### (c, --w8) generate, GPT-3 1.3B bf16, B = {B}, prompt {prompt}, {new} new tokens, greedy, whole call "
+          f"(prefill included), median of {rounds} rounds (min - max)\n")
+    print("| path | ms per call | ms per token | tokens/s |")
+    print("|---|---|---|---|")
+    for (label, _), s in zip(arms, samples):
+        med, lo, hi = statistics.median(s), min(s), max(s)
+        print(f"| {label} | {med:.1f} ({lo:.1f} - {hi:.1f}) | {med / new:.3f} | {B * new / med * 1e3:.0f} |")
+    agree = (outs[0] == outs[1]).float().mean().item()
+    print(f"\ngraph equals eager: bf16 {torch.equal(outs[0], outs[2])}, int8 {torch.equal(outs[1], outs[3])}; "
+          f"{100 * agree:.1f} % of the int8 tokens equal the bf16 ones (random weights)\n")
+
+
 def bench_ragged(rounds, B=8, prompt=128, new=128):
     import paddle_hackathon_amd as paddle
     from paddle_hackathon_amd.models import GPTForPretraining, GPTGenerator, gpt_config
@@ -284,6 +325,7 @@ def main():
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--ragged", action="store_true", help="part (d): prompts of different lengths")
     ap.add_argument("--beams", type=int, default=0, help="parts (e) and (f): beam search with this many beams")
+    ap.add_argument("--w8", action="store_true", help="part (c): weight_only=\"int8\" against the bf16 weights")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate needs a GPU")
@@ -294,7 +336,7 @@ def main():
         if not a.skip_lm_head:
             bench_lm_head(a.rounds, a.iters)
         if not a.skip_model:
-            bench_generate(a.rounds)
+            (bench_generate_w8 if a.w8 else bench_generate)(a.rounds)
         if a.ragged:
             bench_ragged(a.rounds)
         if a.beams:
