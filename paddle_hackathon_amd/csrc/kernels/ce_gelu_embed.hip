@@ -3,6 +3,9 @@
 // softmax_ce: one 256-thread block per row, single pass with an online
 //   (max, sum-exp) pair per thread merged across the block — the logits row is
 //   read once in forward; backward re-reads it once and writes dlogits once.
+//   The forward keeps the row max m and log(sum exp(x - m)) apart as well as their sum (lse): the
+//   loss (m - x[label]) + log sum and the backward's exp((x - m) - log sum) lose nothing to the
+//   magnitude of the logits, where lse - x would carry the rounding of lse (2e-3 at |x| = 3e4).
 //   Reference: paddle/phi/kernels/gpu/cross_entropy_kernel.cu (hard-label path).
 // bias_gelu: 8-wide vectorised elementwise, exact erf GELU (or tanh approx).
 //   Reference: phi/kernels/gpu/gelu_kernel.cu, operators/fused/fused_dropout_act_bias.h.
@@ -19,7 +22,7 @@ namespace {
 // BERT's 30522: the rows are not 16-B aligned, and the fp32 torch fallback cost ~0.6 ms per step)
 template <typename T, bool VEC = true>
 __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
-                                                             float* __restrict__ loss, float* __restrict__ lse_out,
+                                                             float* __restrict__ loss, float* __restrict__ stats,
                                                              int V, int ignore_index) {
   const long row = blockIdx.x;
   const T* xr = logits + row * (long)V;
@@ -32,6 +35,7 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(const T* __restrict
 #pragma unroll
       for (int i = 1; i < 8; ++i) vm = fmaxf(vm, v[i]);
       const float nm = fmaxf(m, vm);
+      if (nm == -INFINITY) continue;   // only -inf so far (masked / padded vocabulary): exp(-inf + inf) is NaN
       float acc = s * __expf(m - nm);
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc += __expf(v[i] - nm);
@@ -74,34 +78,38 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(const T* __restrict
     float M = sm[0], S = ss[0];
     for (int i = 1; i < 4; ++i) {
       const float nm = fmaxf(M, sm[i]);
+      if (nm == -INFINITY) continue;   // both waves saw -inf only
       S = S * __expf(M - nm) + ss[i] * __expf(sm[i] - nm);
       M = nm;
     }
-    const float lse = M + __logf(S);
-    lse_out[row] = lse;
+    const float ls = __logf(S);
+    const long rows = gridDim.x;
+    stats[row] = M + ls;            // [3][rows]: lse, row max, log sum exp(x - max)
+    stats[rows + row] = M;
+    stats[2 * rows + row] = ls;
     const long lab = labels[row];
     if (lab == ignore_index || lab < 0 || lab >= V) {
       loss[row] = 0.f;
     } else {
-      loss[row] = lse - Cvt<T>::ld(xr, lab);
+      loss[row] = (M - Cvt<T>::ld(xr, lab)) + ls;
     }
   }
 }
 
 template <typename T, bool VEC = true>
 __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __restrict__ gloss, const T* __restrict__ logits,
-                                                             const int64_t* __restrict__ labels, const float* __restrict__ lse,
+                                                             const int64_t* __restrict__ labels, const float* __restrict__ stats,
                                                              T* __restrict__ dx, int V, int ignore_index) {
   const long row = blockIdx.x;
   const long lab = labels[row];
   const bool ign = (lab == ignore_index || lab < 0 || lab >= V);
   const float g = ign ? 0.f : gloss[row];
-  const float l = lse[row];
+  const float mx = stats[(long)gridDim.x + row], ls = stats[2L * gridDim.x + row];   // the forward's [3][rows]
   const T* xr = logits + row * (long)V;
   T* dr = dx + row * (long)V;
   if constexpr (!VEC) {
     for (int c = threadIdx.x; c < V; c += 256) {
-      const float p = __expf(Cvt<T>::ld(xr, c) - l);
+      const float p = __expf((Cvt<T>::ld(xr, c) - mx) - ls);
       Cvt<T>::st(dr, c, g * (p - (c == lab ? 1.f : 0.f)));
     }
     return;
@@ -111,7 +119,7 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __rest
     Vec8<T>::ld(xr + c, v);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const float p = __expf(v[i] - l);
+      const float p = __expf((v[i] - mx) - ls);
       o[i] = g * (p - ((c + i) == lab ? 1.f : 0.f));
     }
     Vec8<T>::st(dr + c, o);
@@ -142,7 +150,9 @@ __device__ __forceinline__ float gelu_grad(float x, bool approx) {
     // work stays well under the HBM time
     // (the shared definition: common.h)
     const float x2 = x * x;
-    return gelu_tanh_grad_sig(x, x2, gelu_tanh_sig(x, x2));
+    float e;
+    const float sg = gelu_tanh_sig_e(x, x2, e);
+    return gelu_tanh_grad_sig(x, x2, sg, e);
   }
   const float cdf = 0.5f * (1.f + erff(x * 0.7071067811865476f));
   const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
@@ -539,26 +549,29 @@ inline int grid_for(long n, int per_block) {
 
 }  // namespace
 
-PHA_API int pha_softmax_ce_fwd(int dt, const void* logits, const int64_t* labels, float* loss, float* lse,
+// stats: [3][rows] fp32 (3 * rows floats are written) — the log-sum-exp of each row, then its two terms
+// (row max, log of the sum of exp(x - max)), which is what pha_softmax_ce_bwd reads
+PHA_API int pha_softmax_ce_fwd(int dt, const void* logits, const int64_t* labels, float* loss, float* stats,
                                long rows, int V, int ignore_index, hipStream_t stream) {
   if (V <= 0) return (int)hipErrorInvalidValue;
   PHA_DISPATCH_T(dt, T, {
     if (V % 8 == 0)
-      hipLaunchKernelGGL((softmax_ce_fwd_kernel<T, true>), dim3(rows), dim3(256), 0, stream, (const T*)logits, labels, loss, lse, V, ignore_index);
+      hipLaunchKernelGGL((softmax_ce_fwd_kernel<T, true>), dim3(rows), dim3(256), 0, stream, (const T*)logits, labels, loss, stats, V, ignore_index);
     else
-      hipLaunchKernelGGL((softmax_ce_fwd_kernel<T, false>), dim3(rows), dim3(256), 0, stream, (const T*)logits, labels, loss, lse, V, ignore_index);
+      hipLaunchKernelGGL((softmax_ce_fwd_kernel<T, false>), dim3(rows), dim3(256), 0, stream, (const T*)logits, labels, loss, stats, V, ignore_index);
   });
   return (int)hipGetLastError();
 }
 
-PHA_API int pha_softmax_ce_bwd(int dt, const float* gloss, const void* logits, const int64_t* labels, const float* lse,
+// stats: the [3][rows] array pha_softmax_ce_fwd wrote
+PHA_API int pha_softmax_ce_bwd(int dt, const float* gloss, const void* logits, const int64_t* labels, const float* stats,
                                void* dx, long rows, int V, int ignore_index, hipStream_t stream) {
   if (V <= 0) return (int)hipErrorInvalidValue;
   PHA_DISPATCH_T(dt, T, {
     if (V % 8 == 0)
-      hipLaunchKernelGGL((softmax_ce_bwd_kernel<T, true>), dim3(rows), dim3(256), 0, stream, gloss, (const T*)logits, labels, lse, (T*)dx, V, ignore_index);
+      hipLaunchKernelGGL((softmax_ce_bwd_kernel<T, true>), dim3(rows), dim3(256), 0, stream, gloss, (const T*)logits, labels, stats, (T*)dx, V, ignore_index);
     else
-      hipLaunchKernelGGL((softmax_ce_bwd_kernel<T, false>), dim3(rows), dim3(256), 0, stream, gloss, (const T*)logits, labels, lse, (T*)dx, V, ignore_index);
+      hipLaunchKernelGGL((softmax_ce_bwd_kernel<T, false>), dim3(rows), dim3(256), 0, stream, gloss, (const T*)logits, labels, stats, (T*)dx, V, ignore_index);
   });
   return (int)hipGetLastError();
 }

@@ -120,9 +120,18 @@ __device__ __forceinline__ float gelu_tanh_sig(float x, float x2) {
   constexpr float c0 = -2.f * k * 1.4426950408889634f, c1 = c0 * c;
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x2, c1, c0)));
 }
-__device__ __forceinline__ float gelu_tanh_grad_sig(float x, float x2, float sg) {
+// s and e = exp(-2u) for the derivative: 1 - s = e s without the cancellation of the subtraction
+// (at x = 4..5, 1 - s is 1e-7 and 1.f - s keeps one bit of it). For x < -9.6 e is inf and s is 0: fminf
+// turns the NaN of inf * 0 into the 1 that 1 - s is there, and the derivative stays exactly 0.
+__device__ __forceinline__ float gelu_tanh_sig_e(float x, float x2, float& e) {
   constexpr float k = 0.7978845608028654f, c = 0.044715f;
-  const float q = x * __builtin_fmaf(x2, 6.f * k * c, 2.f * k) * (1.f - sg);
+  constexpr float c0 = -2.f * k * 1.4426950408889634f, c1 = c0 * c;
+  e = __builtin_amdgcn_exp2f(x * __builtin_fmaf(x2, c1, c0));
+  return __builtin_amdgcn_rcpf(1.f + e);
+}
+__device__ __forceinline__ float gelu_tanh_grad_sig(float x, float x2, float sg, float e) {
+  constexpr float k = 0.7978845608028654f, c = 0.044715f;
+  const float q = x * __builtin_fmaf(x2, 6.f * k * c, 2.f * k) * fminf(e * sg, 1.f);
   return __builtin_fmaf(q, sg, sg);
 }
 

@@ -683,10 +683,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int e2 = 0; e2 < 2; ++e2) {
           const int e = 2 * h + e2;
-          const float a = v0[e], a2 = a * a, sa = gelu_tanh_sig(a, a2);
-          const float b = v1[e], b2 = b * b, sb = gelu_tanh_sig(b, b2);
-          da[e2] = gelu_tanh_grad_sig(a, a2, sa);
-          db[e2] = gelu_tanh_grad_sig(b, b2, sb);
+          float ea, eb;
+          const float a = v0[e], a2 = a * a, sa = gelu_tanh_sig_e(a, a2, ea);
+          const float b = v1[e], b2 = b * b, sb = gelu_tanh_sig_e(b, b2, eb);
+          da[e2] = gelu_tanh_grad_sig(a, a2, sa, ea);
+          db[e2] = gelu_tanh_grad_sig(b, b2, sb, eb);
           v0[e] = a * sa;
           v1[e] = b * sb;
         }

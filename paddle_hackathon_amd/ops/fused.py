@@ -90,7 +90,9 @@ class _Softmax(torch.autograd.Function):
 
 
 def softmax(x, axis=-1):
-    if axis in (-1, x.dim() - 1) and _use_hip(x) and x.dtype in (torch.bfloat16, torch.float32, torch.float16) and x.is_contiguous() and x.shape[-1] <= 16384:
+    # rows the kernel does not take (not whole 16-byte vectors, or wider than its registers) go to torch
+    if (axis in (-1, x.dim() - 1) and _use_hip(x) and x.dtype in (torch.bfloat16, torch.float32, torch.float16)
+            and x.is_contiguous() and x.shape[-1] % 8 == 0 and x.shape[-1] <= _hip._SOFTMAX_MAX_H):
         return _Softmax.apply(x)
     return torch.softmax(x, axis)
 
@@ -237,15 +239,15 @@ def bias_dropout_residual_layer_norm(x, residual, bias, ln_w, ln_b, dropout_p, t
 class _SoftmaxCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ignore_index):
-        loss, lse = _hip.softmax_ce_fwd(logits, labels, ignore_index)
-        ctx.save_for_backward(logits, labels, lse)
+        loss, stats = _hip.softmax_ce_fwd(logits, labels, ignore_index)
+        ctx.save_for_backward(logits, labels, stats)
         ctx.ignore_index = ignore_index
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
-        logits, labels, lse = ctx.saved_tensors
-        gx = _hip.softmax_ce_bwd(gloss.contiguous().float(), logits, labels, lse, ctx.ignore_index)
+        logits, labels, stats = ctx.saved_tensors
+        gx = _hip.softmax_ce_bwd(gloss.contiguous().float(), logits, labels, stats, ctx.ignore_index)
         return gx, None, None
 
 

@@ -212,10 +212,13 @@ def bn_bwd(dy, x, y, w, save_mean, save_istd, relu=False, want_dres=False, affin
     return dx, dwb[0], dwb[1], dres
 
 
+_SOFTMAX_MAX_H = 8192   # the widest row the kernels hold in registers (16 chunks of 512)
+
+
 def softmax_fwd(x):
     H = x.shape[-1]
     rows = x.numel() // H
-    assert H % 8 == 0 and H <= 4096
+    assert H % 8 == 0 and H <= _SOFTMAX_MAX_H
     y = torch.empty_like(x)
     _check(_L().pha_softmax_fwd(_DT[x.dtype], _ptr(x), _ptr(y), rows, H, _stream(x)), "softmax_fwd")
     return y
@@ -224,6 +227,7 @@ def softmax_fwd(x):
 def softmax_bwd(dy, y):
     H = y.shape[-1]
     rows = y.numel() // H
+    assert H % 8 == 0 and H <= _SOFTMAX_MAX_H and dy.shape == y.shape and dy.dtype == y.dtype
     dx = torch.empty_like(y)
     _check(_L().pha_softmax_bwd(_DT[y.dtype], _ptr(dy), _ptr(y), _ptr(dx), rows, H, _stream(y)), "softmax_bwd")
     return dx
@@ -233,19 +237,24 @@ def softmax_bwd(dy, y):
 # cross entropy / gelu / embedding
 # ----------------------------------------------------------------------------
 def softmax_ce_fwd(logits, labels, ignore_index):
+    """(loss [rows], stats [3, rows]) in fp32; stats = (lse, row max m, log sum exp(x - m)): lse is
+    stats[0], the backward takes the whole of stats (it forms x - lse as (x - m) - log sum, which
+    keeps its precision when the logits are large)"""
     rows, V = logits.shape
     assert labels.numel() == rows and V > 0   # V % 8 != 0: the kernels' element-wise path
     loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    _check(_L().pha_softmax_ce_fwd(_DT[logits.dtype], _ptr(logits), _ptr(labels), _ptr(loss), _ptr(lse), rows, V,
+    stats = torch.empty((3, rows), dtype=torch.float32, device=logits.device)
+    _check(_L().pha_softmax_ce_fwd(_DT[logits.dtype], _ptr(logits), _ptr(labels), _ptr(loss), _ptr(stats), rows, V,
                                    int(ignore_index), _stream(logits)), "softmax_ce_fwd")
-    return loss, lse
+    return loss, stats
 
 
-def softmax_ce_bwd(gloss, logits, labels, lse, ignore_index):
+def softmax_ce_bwd(gloss, logits, labels, stats, ignore_index):
+    """stats: the [3, rows] statistics softmax_ce_fwd returned"""
     rows, V = logits.shape
+    assert stats.shape == (3, rows) and stats.dtype == torch.float32 and stats.is_contiguous()
     dx = torch.empty_like(logits)
-    _check(_L().pha_softmax_ce_bwd(_DT[logits.dtype], _ptr(gloss), _ptr(logits), _ptr(labels), _ptr(lse), _ptr(dx), rows, V,
+    _check(_L().pha_softmax_ce_bwd(_DT[logits.dtype], _ptr(gloss), _ptr(logits), _ptr(labels), _ptr(stats), _ptr(dx), rows, V,
                                    int(ignore_index), _stream(logits)), "softmax_ce_bwd")
     return dx
 

@@ -202,7 +202,9 @@ def test_bias_gelu(dt, approx, rows):
 
 
 def test_layer_norm_bwd_two_stage_column_sum():
-    """8192 rows: dgamma/dbeta partials go through the chip-wide two-stage column sum."""
+    """8192 rows x 2048: the strided row loop of the backward's H = 1537..2048 branch (512 blocks of 8
+    rows, 2 passes) and the single-launch column sum of its 512 partial rows (the two-stage column
+    sum needs more than 1024 partials: tests/test_rowwise_edges_gpu.py)."""
     from paddle_hackathon_amd.ops import hip
     torch.manual_seed(0)
     x = torch.randn(8192, 2048, device="cuda").bfloat16()
