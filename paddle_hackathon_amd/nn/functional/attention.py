@@ -16,7 +16,7 @@ from ... import ops as _ops
 
 _w = _wrap
 
-__all__ = ["scaled_dot_product_attention", "flash_attention", "sparse_attention"]
+__all__ = ["scaled_dot_product_attention", "flash_attention", "flash_attn_unpadded", "sparse_attention"]
 
 
 def scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False,
@@ -30,6 +30,20 @@ def flash_attention(query, key, value, dropout=0.0, causal=False, return_softmax
                     rng_name="", training=True, name=None):
     out = _w(_ops.flash_attention(query._t, key._t, value._t, causal, dropout, None, training))
     return out, None
+
+
+def flash_attn_unpadded(query, key, value, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, dropout=0.0,
+                        causal=False, return_softmax=False, fixed_seed_offset=None, rng_name="", training=True,
+                        name=None):
+    """Variable-length attention over sequences packed back to back: query [total_q, heads, head_dim],
+    key / value [total_k, kv_heads, head_dim], int32 cu_seqlens_q / cu_seqlens_k [n + 1] with the
+    boundaries (ops.hip.flash_attention_varlen). Returns (out, None)."""
+    if return_softmax:
+        raise ValueError("flash_attn_unpadded: return_softmax=True is not supported (the probabilities are never "
+                         "materialised)")
+    out = _ops.hip.flash_attention_varlen(query._t, key._t, value._t, cu_seqlens_q._t, cu_seqlens_k._t, max_seqlen_q,
+                                          max_seqlen_k, scale, causal, dropout if training else 0.0)
+    return _w(out), None
 
 
 def sparse_attention(query, key, value, sparse_csr_offset, sparse_csr_columns, key_padding_mask=None,

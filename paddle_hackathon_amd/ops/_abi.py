@@ -65,6 +65,11 @@ SIGNATURES = {
     "pha_fa64_fwd": (I, [I, P, P, P, P, P, I, I, I, I, I, F, I, LG, I, LG, I, LG, I, F, U, P, P, P, P, LG, LG, LG]),
     "pha_fa64_bwd": (I, [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, LG, I, LG, I, LG, I, LG, I, LG, I, F, U,
                          P, P, P, P, LG, LG, LG]),
+    # flash_attn_varlen.hip
+    "pha_fa_varlen_workspace": (LG, [I]),
+    "pha_fa_varlen_fwd": (I, [I, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, LG, I, LG, I, LG, I, P, P]),
+    "pha_fa_varlen_bwd": (I, [I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, LG, I, LG, I, LG, I, LG, I,
+                              LG, I, P, P]),
     # gemm256.hip
     "pha_gemm256_nt": (I, [I, P, P, P, P, LG, LG, LG, LG, LG, LG, I, P, I, I, P]),
     "pha_conv256_fwd": (I, [I, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P, P, P, P, P, P, P,

@@ -1090,6 +1090,163 @@ class FlashAttentionPacked(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------
+# variable-length (packed) flash attention (csrc/kernels/flash_attn_varlen.hip)
+# ----------------------------------------------------------------------------
+FA_VARLEN_MAX_SEQS = 65536   # the prep kernel's one-workgroup scan: 256 threads x runs of up to 256
+
+
+def _varlen_check(q, k, v, cu_q, cu_k):
+    """the argument errors of flash_attention_varlen, the same on every path"""
+    fn = "flash_attention_varlen"
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{fn}: {name} must be a 3-D tensor [tokens, heads, head_dim]")
+    if k.shape != v.shape or k.shape[2] != q.shape[2]:
+        raise ValueError(f"{fn}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: k and v must have one "
+                         "shape and q's head_dim")
+    if k.dtype != q.dtype or v.dtype != q.dtype or k.device != q.device or v.device != q.device:
+        raise ValueError(f"{fn}: q, k and v must share a dtype and a device")
+    if k.shape[1] < 1 or q.shape[1] % k.shape[1]:
+        raise ValueError(f"{fn}: {q.shape[1]} query heads are no multiple of {k.shape[1]} key heads")
+    for name, cu in (("cu_seqlens_q", cu_q), ("cu_seqlens_k", cu_k)):
+        if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 2 \
+                or cu.device != q.device:
+            raise ValueError(f"{fn}: {name} must be an int32 [n + 1] tensor (n >= 1) on {q.device}")
+    if cu_q.numel() != cu_k.numel():
+        raise ValueError(f"{fn}: cu_seqlens_q has {cu_q.numel()} entries, cu_seqlens_k {cu_k.numel()}")
+
+
+def flash_attn_varlen_why_not(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=None):
+    """why the varlen kernels cannot take these arguments, or None: bf16 / fp16 q [Tq, H, D], k / v
+    [Tk, Hk, D] on a GPU, dense, D = 64 or 128, H % Hk == 0, int32 contiguous cu_seqlens [n + 1] with
+    1 <= n <= 65,536, a positive scale"""
+    if _lib.lib is None:
+        return "kernel library not loaded"
+    try:
+        _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k)
+    except ValueError as e:
+        return str(e)
+    if not q.is_cuda:
+        return f"q is on {q.device}, not a GPU"
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        return f"q is {q.dtype}; the kernels take bfloat16 or float16"
+    if q.shape[2] not in (64, 128):
+        return f"head_dim={q.shape[2]}; the kernels take 64 or 128"
+    if q.shape[0] < 1 or k.shape[0] < 1 or q.shape[0] >= 2 ** 31 or k.shape[0] >= 2 ** 31:
+        return f"Tq={q.shape[0]}, Tk={k.shape[0]} tokens"
+    if q.shape[1] > 65535:
+        return f"{q.shape[1]} heads are above the grid's 65,535"
+    n = cu_seqlens_q.numel() - 1
+    if n > FA_VARLEN_MAX_SEQS:
+        return f"n={n} sequences are above the prep kernel's {FA_VARLEN_MAX_SEQS}"
+    if not cu_seqlens_q.is_contiguous() or not cu_seqlens_k.is_contiguous():
+        return "cu_seqlens are not contiguous"
+    if scale is not None and not (0.0 < float(scale) < float("inf")):
+        return f"scale={scale} is not positive"
+    return None
+
+
+def flash_attn_varlen_supported(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=None):
+    return flash_attn_varlen_why_not(q, k, v, cu_seqlens_q, cu_seqlens_k, scale) is None
+
+
+class FlashAttentionVarlen(torch.autograd.Function):
+    """Packed variable-length attention on flash_attn_varlen.hip: q [Tq, H, D], k / v [Tk, Hk, D],
+    int32 device cu_seqlens [n + 1]. Nothing here reads the lengths: the grids come from Tq, Tk and n."""
+
+    @staticmethod
+    def _ws(cu_q):
+        n = cu_q.numel() - 1
+        return n, torch.empty(_L().pha_fa_varlen_workspace(n) // 4, dtype=torch.int32, device=cu_q.device)
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, causal, scale):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        Tq, H, D = q.shape
+        Tk, Hk = k.shape[0], k.shape[1]
+        n, ws = FlashAttentionVarlen._ws(cu_q)
+        o = torch.empty_like(q)
+        lse = torch.empty((H, Tq), dtype=torch.float32, device=q.device)
+        _check(_L().pha_fa_varlen_fwd(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(cu_q),
+                                      _ptr(cu_k), n, Tq, Tk, H, Hk, D, scale, int(causal), H * D, D, Hk * D, D, H * D,
+                                      D, _ptr(ws), _stream(q)), "fa_varlen_fwd")
+        ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
+        ctx.causal, ctx.scale = causal, scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
+        do = do.contiguous()
+        Tq, H, D = q.shape
+        Tk, Hk = k.shape[0], k.shape[1]
+        L = _L()
+        n, ws = FlashAttentionVarlen._ws(cu_q)
+        delta = torch.empty((H, Tq), dtype=torch.float32, device=q.device)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        _check(L.pha_flash_attn_bwd_preprocess(_DT[q.dtype], _ptr(o), _ptr(do), _ptr(delta), 1, Tq, H, D, _stream(q)),
+               "flash_attn_bwd_preprocess")
+        _check(L.pha_fa_varlen_bwd(_DT[q.dtype], _ptr(q), _ptr(k), _ptr(v), _ptr(do), _ptr(lse), _ptr(delta), _ptr(dq),
+                                   _ptr(dk), _ptr(dv), _ptr(cu_q), _ptr(cu_k), n, Tq, Tk, H, Hk, D, ctx.scale,
+                                   int(ctx.causal), H * D, D, Hk * D, D, H * D, D, H * D, D, Hk * D, D, _ptr(ws),
+                                   _stream(q)), "fa_varlen_bwd")
+        return dq, dk, dv, None, None, None, None
+
+
+def _flash_attn_varlen_composite(q, k, v, cu_q, cu_k, scale, causal, dropout_p):
+    """the same contract sequence by sequence in plain torch (reads cu_seqlens on the host)"""
+    bq, bk = cu_q.tolist(), cu_k.tolist()
+    Tq, Tk, G = q.shape[0], k.shape[0], q.shape[1] // k.shape[1]
+    acc = torch.float64 if q.dtype == torch.float64 else torch.float32
+    out = torch.zeros_like(q)
+    for i in range(len(bq) - 1):
+        s, e = min(max(bq[i], 0), Tq), min(max(bq[i + 1], 0), Tq)
+        ks, ke = min(max(bk[i], 0), Tk), min(max(bk[i + 1], 0), Tk)
+        if e <= s or ke <= ks:
+            continue
+        qi = q[s:e].to(acc).transpose(0, 1)
+        ki = k[ks:ke].to(acc).transpose(0, 1).repeat_interleave(G, 0)
+        vi = v[ks:ke].to(acc).transpose(0, 1).repeat_interleave(G, 0)
+        sc = (qi @ ki.transpose(1, 2)) * scale
+        if causal:   # top-left aligned: query a sees keys b <= a
+            sc = sc.masked_fill(torch.ones(e - s, ke - ks, dtype=torch.bool, device=q.device).triu(1), float("-inf"))
+        p = torch.softmax(sc, -1)
+        if dropout_p:
+            p = torch.nn.functional.dropout(p, dropout_p)
+        out[s:e] = (p @ vi).transpose(0, 1).to(q.dtype)
+    return out
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale=None, causal=False,
+                           dropout_p=0.0):
+    """Attention over n sequences packed back to back: q [Tq, H, D], k / v [Tk, Hk, D]; sequence i owns
+    query tokens [cu_seqlens_q[i], cu_seqlens_q[i+1]) and key tokens [cu_seqlens_k[i], cu_seqlens_k[i+1])
+    (int32 [n + 1] on q's device) and attends to nothing else; ``causal`` is top-left aligned per
+    sequence. Returns [Tq, H, D]; tokens at or past cu_seqlens_q[n] get zeros, as does a sequence with
+    no keys. ``max_seqlen_*`` are accepted for API parity and size nothing.
+
+    bf16 / fp16 with D = 64 or 128 on a GPU runs on csrc/kernels/flash_attn_varlen.hip without a host
+    read of the lengths (``flash_attn_varlen_why_not`` names what it does not take). CPU tensors, fp32,
+    other head dims and ``dropout_p > 0`` run a per-sequence composite in plain torch that reads
+    cu_seqlens on the host; on a GPU that is recorded as a fallback. PHA_FA_VARLEN=0 forces it."""
+    import os
+    _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k)
+    sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(q.shape[2]))
+    if q.is_cuda:
+        if os.environ.get("PHA_FA_VARLEN", "1") == "0":
+            why = "PHA_FA_VARLEN=0"
+        elif dropout_p:
+            why = "dropout of the probabilities is not in the varlen kernels"
+        else:
+            why = flash_attn_varlen_why_not(q, k, v, cu_seqlens_q, cu_seqlens_k, sc)
+        if why is None:
+            return FlashAttentionVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, bool(causal), sc)
+        from . import fallback
+        fallback.note("attention_varlen", why + " -> per-sequence torch composite")
+    return _flash_attn_varlen_composite(q, k, v, cu_seqlens_q, cu_seqlens_k, sc, bool(causal), float(dropout_p))
+
+
+# ----------------------------------------------------------------------------
 # split-KV decode attention (csrc/kernels/decode_attn.hip)
 # ----------------------------------------------------------------------------
 def _decode_attn_chunk():
