@@ -42,27 +42,12 @@
 // instead of a dependent 4-byte load in front of every key's 16-byte loads). BEAM is one more
 // template parameter of the partial kernel; the scalar and per-row instantiations are the code they
 // were before.
-#include "common.h"
+#include "decode_attn_common.h"
 
 namespace pha {
 
-constexpr int DECODE_ATTN_CHUNK = 128;
-constexpr int DECODE_ATTN_THREADS = 256;
-constexpr int DECODE_ATTN_WAVES = DECODE_ATTN_THREADS / 64;
-
 __device__ __forceinline__ void raw_ld8(const bf16_t* p, uint4& r) { r = *reinterpret_cast<const uint4*>(p); }
 __device__ __forceinline__ void raw_ld8(const half_t* p, uint4& r) { r = *reinterpret_cast<const uint4*>(p); }
-
-// merge the online-softmax state (m2, l2, o2) into (m, l, o); either side may be empty (m = -inf)
-__device__ __forceinline__ void osm_merge(float& m, float& l, float (&o)[8], float m2, float l2, const float (&o2)[8]) {
-  const float mn = fmaxf(m, m2);
-  const float a = (m == -INFINITY) ? 0.f : __expf(m - mn);
-  const float b = (m2 == -INFINITY) ? 0.f : __expf(m2 - mn);
-  l = l * a + l2 * b;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = o[j] * a + o2[j] * b;
-  m = mn;
-}
 
 // the beam form's staged table entries; only that form instantiates it
 __device__ __forceinline__ int* beam_rows() {
@@ -265,32 +250,6 @@ __global__ __launch_bounds__(DECODE_ATTN_THREADS) void decode_attn_partial(
     for (int j = 0; j < 8; ++j) wrow[sub * 8 + j] = o[j];
     if (sub == 0) { wrow[D] = m; wrow[D + 1] = l; }
   }
-}
-
-// one thread per element of D; out: [B, H * D]
-template <typename T, bool ROWS>
-__global__ void decode_attn_combine(const float* __restrict__ ws, T* __restrict__ out, int ts_host,
-                                    const int* __restrict__ ts_dev, int H, int D, int max_seq, int nsplit) {
-  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-  const size_t bh = (size_t)b * H + h;
-  const int ts = ROWS ? ts_dev[b] : (ts_dev ? *ts_dev : ts_host);
-  if (ts < 0 || ts >= max_seq) {
-    Cvt<T>::st(out, bh * D + d, __builtin_nanf(""));
-    return;
-  }
-  const int nlive = ts / DECODE_ATTN_CHUNK + 1;    // <= nsplit because ts < max_seq
-  const float* row = ws + bh * nsplit * (D + 2);
-  float M = -INFINITY;
-  for (int s = 0; s < nlive; ++s) M = fmaxf(M, row[(size_t)s * (D + 2) + D]);
-  float acc = 0.f, L = 0.f;
-  for (int s = 0; s < nlive; ++s) {
-    const float* r = row + (size_t)s * (D + 2);
-    const float ms = r[D];
-    const float w = (ms == -INFINITY) ? 0.f : __expf(ms - M);
-    L += w * r[D + 1];
-    acc += w * r[d];
-  }
-  Cvt<T>::st(out, bh * D + d, L > 0.f ? acc / L : 0.f);   // every key masked out: zeros
 }
 
 // ind / beam: the beam form's table and group size; the plain forms pass null and 1

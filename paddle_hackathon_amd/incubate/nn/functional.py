@@ -254,7 +254,8 @@ def fused_multi_head_attention(x, qkv_weight, linear_weight, pre_layer_norm=Fals
     return _wrap(o)
 
 
-def _decode_kernel_ok(qkv, cache, mask, device_time_step, dropout_rate, training, cache_indirection=None, beam_size=1):
+def _decode_kernel_ok(qkv, cache, mask, device_time_step, dropout_rate, training, cache_indirection=None, beam_size=1,
+                      cache_scales=None):
     """whether one decode step's attention (qkv [B, 3, H, D], the layer's cache) runs on the split-KV
     decode kernels (ops/hip.decode_attention). PHA_DECODE_ATTN=0 keeps the composite; on the GPU
     every other reason to keep it is recorded as a fallback."""
@@ -264,7 +265,8 @@ def _decode_kernel_ok(qkv, cache, mask, device_time_step, dropout_rate, training
         reason = "attention dropout"
     elif torch.is_grad_enabled() and qkv.requires_grad:
         reason = "needs a gradient (the decode kernels have no backward; run generation under no_grad)"
-    elif not _ops.hip.decode_attn_supported(qkv, cache, mask, device_time_step, cache_indirection, beam_size):
+    elif not _ops.hip.decode_attn_supported(qkv, cache, mask, device_time_step, cache_indirection, beam_size,
+                                            cache_scales):
         reason = (f"{qkv.dtype} D={qkv.shape[-1]} cache {cache.dtype} {tuple(cache.shape)} "
                   f"mask={None if mask is None else tuple(mask.shape)}")
     else:
@@ -343,13 +345,55 @@ def _decode_beam_composite(q, k, v, c, ts_rows, ind, beam, mask, dropout_rate, t
     return _decode_rows_composite(q, k, v, tmp, ts_rows, extra, dropout_rate, training, mode)
 
 
+def _q8_scales_check(cache_kvs, cache_kv_scales, n_layers, device):
+    """the ValueErrors of ``cache_kv_scales``; True where the caches are int8"""
+    fn = "fused_multi_transformer"
+    q8 = cache_kv_scales is not None
+    if cache_kvs is None:
+        if q8:
+            raise ValueError(f"{fn}: cache_kv_scales needs cache_kvs")
+        return False
+    if any((_u(c).dtype == torch.int8) != q8 for c in cache_kvs):
+        raise ValueError(f"{fn}: int8 caches and cache_kv_scales go together (one fp32 [2, B, H, max_seq] tensor per layer)")
+    if q8:
+        if len(cache_kv_scales) != n_layers or len(cache_kvs) != n_layers:
+            raise ValueError(f"{fn}: cache_kv_scales has {len(cache_kv_scales)} entries for {n_layers} layers")
+        for c, t in zip(cache_kvs, cache_kv_scales):
+            c, t = _u(c), _u(t)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(c.shape[:4]) \
+                    or t.device != c.device or c.device != device:
+                raise ValueError(f"{fn}: every cache_kv_scales entry must be a float32 {list(c.shape[:4])} tensor on "
+                                 f"{device}, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', ()))}")
+    return q8
+
+
+def _q8_append(c8, sc, k, v, ts, ts_rows):
+    """quantise the new keys and values ``k`` / ``v`` [B, H, S, D] by the cache rule, store them with their
+    scales at [ts, ts + S) (``ts`` an int; None with ``ts_rows``: row b at ts_rows[b], rows whose step is
+    outside the cache left alone) and return the pair as its readers see it"""
+    (kq, ks), (vq, vs) = _ops.hip.kv_cache_quantize(k), _ops.hip.kv_cache_quantize(v)
+    if ts_rows is None:
+        S = k.shape[2]
+        c8[0, :, :, ts:ts + S], c8[1, :, :, ts:ts + S] = kq, vq
+        sc[0, :, :, ts:ts + S], sc[1, :, :, ts:ts + S] = ks, vs
+    else:
+        idx = ts_rows.reshape(-1).long()
+        ok = ((idx >= 0) & (idx < c8.shape[3]))[:, None]
+        idx = idx.clamp(0, c8.shape[3] - 1)
+        rows = torch.arange(c8.shape[1], device=c8.device)
+        for p, (q, s) in enumerate(((kq, ks), (vq, vs))):
+            c8[p][rows, :, idx] = torch.where(ok[..., None], q[:, :, 0], c8[p][rows, :, idx])
+            sc[p][rows, :, idx] = torch.where(ok, s[:, :, 0], sc[p][rows, :, idx])
+    return _ops.hip.kv_cache_dequantize(kq, ks, k.dtype), _ops.hip.kv_cache_dequantize(vq, vs, v.dtype)
+
+
 def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, linear_weights, linear_biases,
                             ffn_ln_scales, ffn_ln_biases, ffn1_weights, ffn1_biases, ffn2_weights, ffn2_biases,
                             pre_layer_norm=True, epsilon=1e-05, cache_kvs=None, time_step=None, attn_mask=None,
                             dropout_rate=0.0, activation="gelu", training=False, mode="upscale_in_train",
                             trans_qkvw=True, ring_id=-1, name=None, cache_indirection=None, beam_size=1,
                             qkv_weight_scales=None, linear_weight_scales=None, ffn1_weight_scales=None,
-                            ffn2_weight_scales=None):
+                            ffn2_weight_scales=None, cache_kv_scales=None):
     """Stack of pre-LN decoder layers for generation. ``cache_kvs[i]`` is a preallocated
     [2, B, H, max_seq, D] buffer updated in place: context stage (time_step None) writes
     positions [0, S); decode stage (S == 1) writes position ``time_step`` and attends over
@@ -383,9 +427,21 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     ``[3, H, D, E]`` with scales ``[3 * H * D]``; ``trans_qkvw=False`` is a ``ValueError``). With at most 16
     rows on the GPU every product runs on the int8 weight-streaming kernel (csrc/kernels/skinny_w8.hip),
     bias / activation / residual fused as above; in the context stage and on the CPU the weight is
-    dequantised to the input's dtype, one temporary at a time, and the product runs as it does today."""
+    dequantised to the input's dtype, one temporary at a time, and the product runs as it does today.
+
+    Int8 KV cache: ``cache_kv_scales`` is a list with one fp32 ``[2, B, H, max_seq]`` tensor per layer, and
+    ``cache_kvs[i]`` is then int8; both are updated in place. A key or value row, rounded to the dtype of
+    ``x``, is stored as ``q = round(row / scale)`` with ``scale = absmax / 127`` (``ops.hip.kv_cache_quantize``)
+    and read as ``float(q) * scale``, from the step that appends it on. On the GPU the decode stage runs on
+    the int8 form of the kernel pair (csrc/kernels/decode_attn_q8.hip) under the conditions above, and the
+    context stage attends over the unquantised keys and values while a store kernel fills the cache. On the
+    CPU, and for what the kernels do not take, the live cache is dequantised, today's path runs on it and the
+    written positions are quantised by the same rule (on the GPU recorded as a fallback). Scales without an
+    int8 cache or the reverse, a list of the wrong length and scales of a wrong shape, dtype or device are
+    a ``ValueError``."""
     h = _u(x)
     B, S, E = h.shape
+    q8 = _q8_scales_check(cache_kvs, cache_kv_scales, len(qkv_weights), h.device)
     w8 = (qkv_weight_scales, linear_weight_scales, ffn1_weight_scales, ffn2_weight_scales)
     if any(s is not None for s in w8) and any(s is None for s in w8):
         raise ValueError("fused_multi_transformer: give all four of qkv_weight_scales, linear_weight_scales, "
@@ -467,8 +523,9 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             # goes into this product's epilogue
             use_decode = decode and _decode_kernel_ok(a2.as_strided((B, 3, H, D), (0, 0, 0, 0)), _u(cache_kvs[i]), mask,
                                                       ts_dev if ts_dev is not None else False, dropout_rate,
-                                                      training, ind, beam_size)
-            qbe = None if use_decode or qb is None else qb.reshape(-1)
+                                                      training, ind, beam_size, _u(cache_kv_scales[i]) if q8 else None)
+            # (nor with an int8 cache: its rows are quantised from the product rounded first, as the kernels do)
+            qbe = None if use_decode or qb is None or q8 else qb.reshape(-1)
             if qbe is not None and not (_ops.hip.skinny_gemm_supported(a2, w2, tq, qbe) if qs is None else
                                         _ops.hip.skinny_gemm_w8_supported(a2, w2, qs, qbe)):
                 qbe = None   # added below as today
@@ -479,7 +536,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             qkv = a2 @ (w2.t() if tq else w2)
             use_decode = decode and _decode_kernel_ok(qkv.reshape(B, 3, H, D), _u(cache_kvs[i]), mask,
                                                       ts_dev if ts_dev is not None else False, dropout_rate, training,
-                                                      ind, beam_size)
+                                                      ind, beam_size, _u(cache_kv_scales[i]) if q8 else None)
         if use_decode:
             # one split-KV kernel pair: bias add, cache append and attention over [0, time_step]
             if qb is not None and (qb.dtype != qkv.dtype or not qb.is_contiguous()):
@@ -487,28 +544,47 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             if ind is not None:
                 o = _ops.hip.decode_attention(qkv.reshape(B, 3, H, D), None if qb is None else qb.reshape(3, H, D),
                                               _u(cache_kvs[i]), ts_dev, mask, cache_indirection=ind,
-                                              beam_size=beam_size)
+                                              beam_size=beam_size, cache_scales=_u(cache_kv_scales[i]) if q8 else None)
             else:
                 o = _ops.hip.decode_attention(qkv.reshape(B, 3, H, D), None if qb is None else qb.reshape(3, H, D),
-                                              _u(cache_kvs[i]), ts_dev if ts_dev is not None else ts, mask)
+                                              _u(cache_kvs[i]), ts_dev if ts_dev is not None else ts, mask,
+                                              cache_scales=_u(cache_kv_scales[i]) if q8 else None)
         else:
             if ts_dev is not None and ts is None and ts_rows is None:
                 ts = int(ts_dev.item())
             if qb is not None:
                 qkv = qkv + qb.reshape(-1)
-            qkv = qkv.reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
+            qkv5 = qkv.reshape(B, S, 3, H, D)
+            qkv = qkv5.permute(2, 0, 3, 1, 4)
             q, k, v = qkv[0], qkv[1], qkv[2]
             causal = False
+            c = _u(cache_kvs[i]) if cache_kvs is not None else None
+            if q8:
+                c8, csc = c, _u(cache_kv_scales[i])
+                if ts is None and ts_rows is None:
+                    # context stage: attention over the unquantised k / v below; the cache gets the quantised rows
+                    c = None
+                    if k.is_cuda and _ops.fused._use_hip(k) and _ops.hip.kv_cache_store_supported(qkv5, c8, csc):
+                        _ops.hip.kv_cache_store(qkv5, c8, csc)
+                    else:
+                        if k.is_cuda:
+                            from ...ops import fallback
+                            fallback.note("kv_cache_store", f"{k.dtype} D={D} cache {tuple(c8.shape)} -> torch composite")
+                        _q8_append(c8, csc, k, v, 0, None)
+                else:
+                    # what the decode kernels do not take: dequantise the cache, quantise the new rows and run
+                    # today's path on both (it writes the dequantised new rows into the temporary)
+                    c = _ops.hip.kv_cache_dequantize(c8, csc, k.dtype)
+                    k, v = _q8_append(c8, csc, k, v, ts, ts_rows)
             if ind is not None:
-                o = _decode_beam_composite(q, k, v, _u(cache_kvs[i]), ts_rows, ind, beam_size, mask, dropout_rate,
-                                           training, mode)
+                o = _decode_beam_composite(q, k, v, c, ts_rows, ind, beam_size, mask, dropout_rate, training, mode)
             elif ts_rows is not None:
-                o = _decode_rows_composite(q, k, v, _u(cache_kvs[i]), ts_rows, mask, dropout_rate, training, mode)
+                o = _decode_rows_composite(q, k, v, c, ts_rows, mask, dropout_rate, training, mode)
             elif cache_kvs is not None:
-                c = _u(cache_kvs[i])
                 if ts is None:
-                    c[0, :, :, :S] = k
-                    c[1, :, :, :S] = v
+                    if c is not None:
+                        c[0, :, :, :S] = k
+                        c[1, :, :, :S] = v
                     causal = mask is None
                 else:
                     c[0, :, :, ts:ts + S] = k

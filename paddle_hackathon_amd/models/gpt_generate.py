@@ -40,6 +40,11 @@ order and takes the place of the bf16 copy. The decode step streams them through
 weight-streaming kernel (csrc/kernels/skinny_w8.hip), half the bytes per token; the prefill runs on the
 same weights dequantised, so the prompt and the continuation see one model. The embedding and the LM
 head stay as they are.
+
+``cache_dtype="int8"`` keeps the KV caches as int8 with one fp32 scale per (K or V, row, head, position),
+D + 4 bytes per row instead of 2 D: the prefill quantises the prompt's keys and values with a store
+kernel, and the decode step appends and reads them on the int8 form of the decode kernels
+(csrc/kernels/decode_attn_q8.hip). Scales are formed when a row is appended, so no calibration is needed.
 """
 from __future__ import annotations
 
@@ -59,12 +64,15 @@ class _State:
     """the static buffers of one decode step over R rows (the batch, or batch * beams for beam search),
     and its captured graph once that exists"""
 
-    def __init__(self, R, cache_len, cfg, dtype, device, ts_per_row, beam):
+    def __init__(self, R, cache_len, cfg, dtype, device, ts_per_row, beam, cache_dtype=None):
         H, D = cfg.num_heads, cfg.head_dim
 
         def zeros(dt, *shape):
             return torch.zeros(*shape, dtype=dt, device=device)
-        self.caches = [zeros(dtype, 2, R, H, cache_len, D) for _ in range(cfg.num_layers)]
+        self.caches = [zeros(torch.int8 if cache_dtype == "int8" else dtype, 2, R, H, cache_len, D)
+                       for _ in range(cfg.num_layers)]
+        # cache_dtype="int8": one fp32 scale per (K or V, row, head, position) of every layer's cache
+        self.scales = [zeros(torch.float32, 2, R, H, cache_len) for _ in self.caches] if cache_dtype == "int8" else None
         self.tok = zeros(torch.int64, R)
         self.ts = zeros(torch.int32, R if ts_per_row else 1)   # one element: every row is at the same step
         self.finished = zeros(torch.uint8, R)
@@ -83,7 +91,8 @@ class _State:
 
     def reset(self):
         """a kept state before its next call"""
-        for t in self.caches + [self.finished] + ([] if self.ind is None else [self.lens, self.ind]):
+        for t in self.caches + (self.scales or []) + [self.finished] \
+                + ([] if self.ind is None else [self.lens, self.ind]):
             t.zero_()
 
 
@@ -95,11 +104,13 @@ class GPTGenerator:
         self._qkv = {}        # layer index -> (weight version, bias version, repacked weight, repacked bias)
         self._w8 = {}         # layer index -> (parameter versions, [qkv q, scale, out q, scale, f1 q, scale, f2 q, scale,
         #                       repacked qkv bias]): the int8 copies of weight_only="int8"
-        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged, weight_only)
-        #                       -> _State; (B, cache length, "beam_search", num_beams, eos, weight_only) -> _State
+        self._graphs = {}     # (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged, weight_only,
+        #                       cache_dtype) -> _State;
+        #                       (B, cache length, "beam_search", num_beams, eos, weight_only, cache_dtype) -> _State
         self._eager = set()   # keys whose warm-up step left the kernel path: not tried again
         self.captures = 0     # hipGraph captures so far (a second generate call adds none)
         self.last_caches = None
+        self.last_cache_scales = None   # with cache_dtype="int8": the fp32 scales of last_caches, else None
         self.last_steps = 0   # decode steps the last call ran (fewer than max_new_tokens - 1 after an early stop)
 
     def clear(self):
@@ -182,14 +193,14 @@ class GPTGenerator:
             w["f2_b"].append(layer.mlp.linear2.bias._t)
         return [w[k] for k in names]
 
-    def _stack(self, x, weights, caches, time_step=None, **beam):
+    def _stack(self, x, weights, caches, time_step=None, cache_scales=None, **beam):
         from ..incubate.nn import functional as FF
         scales = dict(zip(("qkv_weight_scales", "linear_weight_scales", "ffn1_weight_scales", "ffn2_weight_scales"),
                           weights[12:]))   # int8 weights: QKV [3, H, D, E], the trans_qkvw layout
         out, _ = FF.fused_multi_transformer(x, *weights[:12], pre_layer_norm=True,
                                             epsilon=self.model.cfg.layer_norm_eps, cache_kvs=caches,
                                             time_step=time_step, activation="gelu_tanh", trans_qkvw=bool(scales),
-                                            **scales, **beam)
+                                            cache_kv_scales=cache_scales, **scales, **beam)
         return out._t
 
     def _logits(self, h):
@@ -216,7 +227,7 @@ class GPTGenerator:
         x = _ops.fused.embedding(st.tok, emb.word_embeddings.weight._t) \
             + emb.position_embeddings.weight._t.index_select(0, st.ts)
         beam = {} if st.ind is None else dict(cache_indirection=st.ind, beam_size=s["beams"])
-        h = self._stack(x.unsqueeze(1), weights, st.caches, st.ts if host_ts is None else host_ts, **beam)
+        h = self._stack(x.unsqueeze(1), weights, st.caches, st.ts if host_ts is None else host_ts, st.scales, **beam)
         logits = self._logits(h.reshape(h.shape[0], -1))
         if st.ind is None:
             out = self._sample(logits, st.u, st.finished, s)
@@ -271,7 +282,7 @@ class GPTGenerator:
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, decode_strategy="greedy_search", temperature=1.0, top_k=0, top_p=1.0,
                  eos_token_id=None, pad_token_id=0, seed=None, use_graph=None, seq_lens=None, attention_mask=None,
-                 num_beams=None, num_return_sequences=1, length_penalty=0.0, weight_only=None):
+                 num_beams=None, num_return_sequences=1, length_penalty=0.0, weight_only=None, cache_dtype=None):
         """``max_new_tokens`` tokens after ``input_ids`` [B, prompt]: (ids int64 [B, max_new_tokens],
         scores fp32 [B, max_new_tokens]), the score being the log probability of the token under the
         temperature-scaled, unfiltered softmax (0 at padded positions).
@@ -306,7 +317,7 @@ class GPTGenerator:
         shape, the log probability of each token along the beam's own history (0 at padded
         positions), so a row of scores sums to the beam's score. ``num_beams=1`` is greedy search, bit
         for bit. The step runs R = B * K rows; up to 16 rows it stays on the kernels and is captured
-        like the other strategies (the graph is kept per (B, cache length, num_beams, eos, weight_only)), above
+        like the other strategies (the graph is kept per (B, cache length, num_beams, eos, weight_only, cache_dtype)), above
         that it runs eagerly on the composites and library GEMMs (recorded as fallbacks). The prompt
         is prefilled once per item, not once per beam.
 
@@ -319,14 +330,20 @@ class GPTGenerator:
         are untouched, and the embedding and the LM head stay in the model's dtype. The mode is part of
         every graph key. Any other value is a ``ValueError``.
 
+        ``cache_dtype`` "int8" keeps the KV caches as int8 with one fp32 scale per (K or V, row, head,
+        position), formed when the row is appended (``ops.hip.kv_cache_quantize``): about half the cache
+        bytes per decode step and per row of context, for every strategy and both ``weight_only`` modes.
+        ``last_caches`` are then int8 and ``last_cache_scales`` their scales. The mode is part of every
+        graph key. None keeps the caches in the model's dtype; any other value is a ``ValueError``.
+
         The model must be in eval mode with ``tensor_parallel_degree == 1``, and
         ``longest prompt + max_new_tokens <= max_position_embeddings``.
 
         ``use_graph`` None captures the decode step in one hipGraph when the model is on the GPU and
         a warm-up step took the kernel path everywhere (no recorded fallback, device-side time step);
         True insists on it, False runs the same step eagerly. The graph and its static buffers are kept
-        on the generator per (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged, weight_only), KV
-        caches included; ``GPTGenerator.clear()`` releases them. The prompt lengths are data of the
+        on the generator per (B, cache length, strategy, temperature, top_k, top_p, eos, pad, ragged, weight_only,
+        cache_dtype), KV caches included; ``GPTGenerator.clear()`` releases them. The prompt lengths are data of the
         ragged graph, not part of its key: one capture serves every mix of lengths with the same
         longest prompt."""
         model, cfg = self.model, self.model.cfg
@@ -338,6 +355,8 @@ class GPTGenerator:
             raise ValueError(f"generate: decode_strategy must be one of {STRATEGIES}, got {decode_strategy!r}")
         if weight_only not in (None, "int8"):
             raise ValueError(f"generate: weight_only={weight_only!r}: None or 'int8' (the only weight-only type there is)")
+        if cache_dtype not in (None, "int8"):
+            raise ValueError(f"generate: cache_dtype={cache_dtype!r}: None (the model's dtype) or 'int8'")
         beam = decode_strategy == "beam_search"
         if num_beams is None:
             if beam:   # there is no default width: the cost of a call is B * num_beams rows per step
@@ -379,11 +398,11 @@ class GPTGenerator:
             if num_beams > cfg.vocab_size:
                 raise ValueError(f"generate: num_beams={num_beams} exceeds the vocabulary ({cfg.vocab_size})")
             s.update(beams=num_beams, nret=num_return_sequences, length_penalty=float(length_penalty))
-            return self._generate_beam(ids_in, lens, n_new, s, use_graph, weight_only)
+            return self._generate_beam(ids_in, lens, n_new, s, use_graph, weight_only, cache_dtype)
         key = (B, cache_len, s["strategy"], s["temperature"], s["top_k"], s["top_p"], s["eos"], s["pad"], ragged,
-               weight_only)
+               weight_only, cache_dtype)
         weights = self._layer_weights(weight_only)
-        st, want_graph = self._state_for(key, B, cache_len, ragged, False, use_graph, n_new)
+        st, want_graph = self._state_for(key, B, cache_len, ragged, False, use_graph, n_new, cache_dtype)
 
         # uniforms of every step, drawn up front (no per-step generator state in a captured graph)
         gen = None
@@ -397,7 +416,7 @@ class GPTGenerator:
         # prefill: the context stage fills the caches; the first token comes from the last position
         # (of each row's own prompt where the lengths differ)
         x = model.gpt.embeddings(_wrap(ids_in))._t
-        h = self._stack(x, weights, st.caches)
+        h = self._stack(x, weights, st.caches, cache_scales=st.scales)
         if ragged:
             ts0 = torch.tensor(lens, dtype=torch.int32).to(dev)
             last = h[torch.arange(B, device=dev), ts0.long() - 1]
@@ -415,7 +434,7 @@ class GPTGenerator:
                      host_ts=None if wte.is_cuda or ragged else P)
         return _wrap(out_ids), _wrap(out_lp)
 
-    def _state_for(self, key, R, cache_len, ts_per_row, beam, use_graph, n_new):
+    def _state_for(self, key, R, cache_len, ts_per_row, beam, use_graph, n_new, cache_dtype=None):
         """(state, want_graph): whether this call is to replay a captured step, and its state: the one
         kept under ``key`` with its graph, reset, or a new one"""
         wte = self.model.gpt.embeddings.word_embeddings.weight._t
@@ -423,10 +442,10 @@ class GPTGenerator:
             and (bool(use_graph) or key not in self._eager)
         st = self._graphs.get(key) if want_graph else None
         if st is None:
-            st = _State(R, cache_len, self.model.cfg, wte.dtype, wte.device, ts_per_row, beam)
+            st = _State(R, cache_len, self.model.cfg, wte.dtype, wte.device, ts_per_row, beam, cache_dtype)
         else:
             st.reset()
-        self.last_caches = st.caches
+        self.last_caches, self.last_cache_scales = st.caches, st.scales
         return st, want_graph
 
     def _decode(self, key, st, weights, s, want_graph, required, n_new, outs, U=None, host_ts=None):
@@ -474,11 +493,12 @@ class GPTGenerator:
         # the sampling composite is captured like the kernel; the beam composite is not
         clean = fallback.total() == before and os.environ.get("PHA_DECODE_ATTN", "1") != "0" \
             and (st.ind is None or os.environ.get("PHA_BEAM_KERNEL", "1") != "0") \
-            and st.caches[0].dtype in (torch.bfloat16, torch.float16) and self.model.cfg.head_dim in (32, 64, 128)
+            and (st.caches[0].dtype in (torch.bfloat16, torch.float16) or st.scales is not None) \
+            and self.model.cfg.head_dim in (32, 64, 128)
         for t, k in zip(st.carried, keep):
             t.copy_(k)
         if not clean and not required:
-            for c in st.caches:   # what the warm-up step appended, at each row's first step
+            for c in st.caches + (st.scales or []):   # what the warm-up step appended, at each row's first step
                 c[:, torch.arange(c.shape[1], device=c.device), :, st.ts.long().expand(c.shape[1])] = 0
             return None
         torch.cuda.synchronize()
@@ -492,22 +512,23 @@ class GPTGenerator:
         return g
 
     # ------------------------------------------------------------------------------ beam search
-    def _generate_beam(self, ids_in, lens, n_new, s, use_graph, weight_only=None):
+    def _generate_beam(self, ids_in, lens, n_new, s, use_graph, weight_only=None, cache_dtype=None):
         """generate()'s beam-search branch: ``ids_in`` [B, P] on the device, ``lens`` the prompt
         lengths or None"""
         model, dev = self.model, ids_in.device
         B, P = ids_in.shape
         K, eos = s["beams"], s["eos"]
         R, cache_len = B * K, P + n_new
-        key = (B, cache_len, "beam_search", K, eos, weight_only)
+        key = (B, cache_len, "beam_search", K, eos, weight_only, cache_dtype)
         weights = self._layer_weights(weight_only)
-        st, want_graph = self._state_for(key, R, cache_len, True, True, use_graph, n_new)
+        st, want_graph = self._state_for(key, R, cache_len, True, True, use_graph, n_new, cache_dtype)
         # per group: beam 0 starts at 0, the others at -inf, so the first step's K picks all continue beam 0
         st.cum.copy_(torch.tensor([0.0] + [float("-inf")] * (K - 1), dtype=torch.float32).repeat(B))
 
         # prefill over the B prompts only, into beam 0's cache row of every group (a strided view)
         x = model.gpt.embeddings(_wrap(ids_in))._t
-        h = self._stack(x, weights, [c[:, ::K] for c in st.caches])
+        h = self._stack(x, weights, [c[:, ::K] for c in st.caches],
+                        cache_scales=None if st.scales is None else [c[:, ::K] for c in st.scales])
         if lens is not None and min(lens) != P:
             ts0 = torch.tensor(lens, dtype=torch.int32).to(dev)
             last = h[torch.arange(B, device=dev), ts0.long() - 1]

@@ -46,6 +46,9 @@ SIGNATURES = {
     "pha_decode_attn": (I, [I, P, P, P, P, LG, LG, F, I, P, P, P, I, I, I, I, P]),
     "pha_decode_attn_rows": (I, [I, P, P, P, P, LG, LG, F, P, P, P, I, I, I, I, P]),
     "pha_decode_attn_beam": (I, [I, P, P, P, P, LG, LG, F, P, P, I, P, P, I, I, I, I, P]),
+    # decode_attn_q8.hip
+    "pha_decode_attn_q8": (I, [I, P, P, P, P, P, LG, LG, F, I, P, I, P, I, P, P, I, I, I, I, P]),
+    "pha_kv_q8_store": (I, [I, P, P, P, LG, LG, I, I, I, I, I, P]),
     # flash_attn.hip
     "pha_flash_attn_fwd_ext": (I, [I, P, P, P, P, P, I, I, I, I, I, I, F, I, P, LG, LG, LG, F, U, P, P]),
     "pha_flash_attn_bwd_ext": (I, [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P, LG, LG, LG, F, U, P, LG,

@@ -1268,7 +1268,38 @@ def _cache_indirection_why_not(cache_indirection, beam_size, B, max_seq, device)
     return None
 
 
-def decode_attn_supported(qkv, cache, mask=None, device_time_step=False, cache_indirection=None, beam_size=1):
+def kv_cache_quantize(x):
+    """the int8 KV-cache rule as a torch composite: ``x`` [..., D] (already in the storage dtype) ->
+    (int8 [..., D], fp32 scale [...]), symmetric per row in fp32: ``scale = absmax / 127`` (1 for a row
+    that is all zero), ``q = clamp(round(x / scale), -127, 127)`` with round half to even. Bit for bit
+    what csrc/kernels/decode_attn_q8.hip stores."""
+    xf = x.detach().to(torch.float32)
+    absmax = xf.abs().amax(-1)
+    # a tensor divisor: torch multiplies by the reciprocal of a Python scalar on the GPU, which is not the
+    # correctly rounded quotient the kernels form
+    scale = torch.where(absmax > 0, absmax / torch.full_like(absmax, 127.0), torch.ones_like(absmax))
+    q = torch.round(xf / scale[..., None]).clamp_(-127, 127).to(torch.int8)
+    return q, scale
+
+
+def kv_cache_dequantize(q, scale, dtype=torch.float32):
+    """int8 ``q`` [..., D] with its fp32 ``scale`` [...] -> ``float(q) * scale`` in fp32, cast to ``dtype``"""
+    return (q.to(torch.float32) * scale[..., None]).to(dtype)
+
+
+def _cache_scales_why_not(cache, cache_scales):
+    """why ``cache_scales`` does not go with the int8 ``cache``, or None"""
+    t = cache_scales
+    if not isinstance(cache, torch.Tensor) or cache.dtype != torch.int8 or cache.dim() != 5:
+        return "cache_scales needs an int8 [2, B, H, max_seq, D] cache"
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(cache.shape[:4]) \
+            or t.device != cache.device or not t.is_contiguous():
+        return f"cache_scales must be a contiguous float32 {list(cache.shape[:4])} tensor on {cache.device}"
+    return None
+
+
+def decode_attn_supported(qkv, cache, mask=None, device_time_step=False, cache_indirection=None, beam_size=1,
+                          cache_scales=None):
     """what the decode kernel takes: a bf16 / fp16 [B, 3, H, D] QKV product with D in 32 / 64 / 128,
     a [2, B, H, max_seq, D] cache of the same dtype and device, and an optional additive / boolean
     mask broadcastable to [B, H, 1, keys] that needs no gradient (with a device time step its key
@@ -1276,12 +1307,18 @@ def decode_attn_supported(qkv, cache, mask=None, device_time_step=False, cache_i
     tensor itself, which is then checked too: int32, on the device of ``qkv``, one element (one step
     for the batch) or B elements (a step per batch row). With ``cache_indirection`` (contiguous int32
     [B, max_seq] on the device of ``qkv``) ``beam_size`` must divide B; without it ``beam_size`` must
-    be 1"""
+    be 1. With ``cache_scales`` (contiguous fp32 [2, B, H, max_seq] on the device) the cache must be int8
+    instead (csrc/kernels/decode_attn_q8.hip)"""
     if not DECODE_ATTN_CHUNK:
         return False
     if not (isinstance(qkv, torch.Tensor) and isinstance(cache, torch.Tensor) and qkv.is_cuda and cache.is_cuda):
         return False
-    if qkv.dtype not in (torch.bfloat16, torch.float16) or cache.dtype != qkv.dtype or cache.device != qkv.device:
+    if qkv.dtype not in (torch.bfloat16, torch.float16) or cache.device != qkv.device:
+        return False
+    if cache_scales is None:
+        if cache.dtype != qkv.dtype:
+            return False
+    elif _cache_scales_why_not(cache, cache_scales) is not None:
         return False
     if qkv.dim() != 4 or qkv.shape[1] != 3 or cache.dim() != 5:
         return False
@@ -1333,7 +1370,8 @@ def _decode_bias(mask, B, H, need, device):
     return mask, (mask.stride(0), mask.stride(1))
 
 
-def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None, cache_indirection=None, beam_size=1):
+def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None, cache_indirection=None, beam_size=1,
+                     cache_scales=None):
     """One decode step of cached attention on the split-KV kernels. ``qkv`` [B, 3, H, D] is the raw
     QKV product of the new token and ``qkv_bias`` [3, H, D] (or None) its bias; the biased key and
     value are written to ``cache`` [2, B, H, max_seq, D] at ``time_step`` in place, and the biased,
@@ -1351,8 +1389,17 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None, cac
     nothing is copied between them. Position ``time_step`` is appended to row b's own cache row;
     ``cache_indirection[b, time_step]`` is not read, and an entry outside [0, K) leaves its key out
     as if masked. The rows of a group must share one step. One entry point serves it with a step
-    per row: a Python int or one-element ``time_step`` is broadcast to [B]. Returns [B, 1, H * D]."""
+    per row: a Python int or one-element ``time_step`` is broadcast to [B]. Returns [B, 1, H * D].
+
+    ``cache_scales`` (contiguous fp32 [2, B, H, max_seq] on the device) makes ``cache`` an int8 cache:
+    the new key and value, rounded to the dtype of ``qkv``, are quantised per (row, head) by
+    ``kv_cache_quantize``'s rule and stored with their scales at ``time_step``; every position is read
+    as ``float(q) * scale``, the new one included. Everything else is as above, for all three forms."""
     fn = "decode_attention"
+    if cache_scales is not None:
+        why = _cache_scales_why_not(cache, cache_scales)
+        if why is not None:
+            raise ValueError(f"{fn}: {why}")
     if isinstance(time_step, torch.Tensor) and isinstance(qkv, torch.Tensor) and qkv.dim() == 4:
         if time_step.dtype != torch.int32 or time_step.device != qkv.device \
                 or time_step.numel() not in (1, qkv.shape[0]) or not time_step.is_contiguous():
@@ -1365,7 +1412,8 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None, cac
         why = _cache_indirection_why_not(cache_indirection, beam_size, qkv.shape[0], cache.shape[3], qkv.device)
         if why is not None:
             raise ValueError(f"{fn}: {why}")
-    if not decode_attn_supported(qkv, cache, mask, isinstance(time_step, torch.Tensor), cache_indirection, beam_size):
+    if not decode_attn_supported(qkv, cache, mask, isinstance(time_step, torch.Tensor), cache_indirection, beam_size,
+                                 cache_scales):
         raise ValueError(f"{fn}: unsupported arguments (see decode_attn_supported)")
     B, _, H, D = qkv.shape
     max_seq = cache.shape[3]
@@ -1386,7 +1434,8 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None, cac
     bias, (sb, sh) = (None, (0, 0))
     if mask is not None:
         bias, (sb, sh) = _decode_bias(mask, B, H, max_seq if ts_dev is not None else ts + 1, dev)
-    tensors = [qkv, cache] + ([qkv_bias] if qkv_bias is not None else [])
+    tensors = [qkv, cache] + ([qkv_bias] if qkv_bias is not None else []) \
+        + ([cache_scales] if cache_scales is not None else [])
     if any(t.data_ptr() % 16 for t in tensors) or (bias is not None and bias.data_ptr() % 4):
         raise ValueError(f"{fn}: qkv, qkv_bias and cache must be 16-byte aligned")
     nsplit = -(-max_seq // DECODE_ATTN_CHUNK)
@@ -1398,6 +1447,13 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None, cac
             ts_dev = torch.full((B,), ts, dtype=torch.int32, device=dev)
         elif ts_dev.numel() != B:
             ts_dev = ts_dev.reshape(1).expand(B).contiguous()
+    if cache_scales is not None:   # one entry point for the three forms
+        _check(_L().pha_decode_attn_q8(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(cache_scales),
+                                       _ptr(bias), sb, sh, sc, ts, _ptr(ts_dev),
+                                       int(ts_dev is not None and ts_dev.numel() > 1), _ptr(cache_indirection),
+                                       int(beam_size), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
+        return out
+    if cache_indirection is not None:
         _check(_L().pha_decode_attn_beam(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc,
                                          _ptr(ts_dev), _ptr(cache_indirection), int(beam_size), _ptr(out), _ptr(ws),
                                          B, H, D, max_seq, _stream(qkv)), fn)
@@ -1409,6 +1465,42 @@ def decode_attention(qkv, qkv_bias, cache, time_step, mask=None, scale=None, cac
     _check(_L().pha_decode_attn(_DT[qkv.dtype], _ptr(qkv), _ptr(qkv_bias), _ptr(cache), _ptr(bias), sb, sh, sc, ts,
                                 _ptr(ts_dev), _ptr(out), _ptr(ws), B, H, D, max_seq, _stream(qkv)), fn)
     return out
+
+
+def kv_cache_store_supported(qkv, cache, cache_scales):
+    """what the prefill store takes: ``qkv`` a contiguous bf16 / fp16 [B, S, 3, H, D] on the GPU with D in
+    32 / 64 / 128; ``cache`` int8 [2, B, H, max_seq, D] with S <= max_seq, dense in its last three
+    dimensions (a strided view over the cache rows, ``c[:, ::K]``, is taken as it is); ``cache_scales``
+    the fp32 [2, B, H, max_seq] view with the same row and plane strides"""
+    if not DECODE_ATTN_CHUNK or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (qkv, cache, cache_scales)):
+        return False
+    if qkv.dtype not in (torch.bfloat16, torch.float16) or qkv.dim() != 5 or qkv.shape[2] != 3 or not qkv.is_contiguous():
+        return False
+    B, S, _, H, D = qkv.shape
+    if D not in (32, 64, 128) or cache.dtype != torch.int8 or cache_scales.dtype != torch.float32 \
+            or cache.device != qkv.device or cache_scales.device != qkv.device:
+        return False
+    if cache.dim() != 5 or tuple(cache.shape[:3]) != (2, B, H) or cache.shape[4] != D or cache.shape[3] < S \
+            or tuple(cache_scales.shape) != tuple(cache.shape[:4]):
+        return False
+    M = cache.shape[3]
+    if tuple(cache.stride()[2:]) != (M * D, D, 1) or tuple(cache_scales.stride()[2:]) != (M, 1):
+        return False
+    sp, sb = cache.stride(0), cache.stride(1)
+    if sb < H * M * D or sb % D or sp % D or cache_scales.stride(0) * D != sp or cache_scales.stride(1) * D != sb:
+        return False
+    return not (qkv.data_ptr() % 16 or cache.data_ptr() % 16 or cache_scales.data_ptr() % 4)
+
+
+def kv_cache_store(qkv, cache, cache_scales):
+    """The prefill store: the keys and values of the biased QKV product ``qkv`` [B, S, 3, H, D] are
+    quantised by ``kv_cache_quantize``'s rule into positions [0, S) of the int8 ``cache`` and of
+    ``cache_scales``, in place (csrc/kernels/decode_attn_q8.hip)."""
+    if not kv_cache_store_supported(qkv, cache, cache_scales):
+        raise ValueError("kv_cache_store: unsupported arguments (see kv_cache_store_supported)")
+    B, S, _, H, D = qkv.shape
+    _check(_L().pha_kv_q8_store(_DT[qkv.dtype], _ptr(qkv), _ptr(cache), _ptr(cache_scales), cache.stride(1),
+                                cache.stride(0), B, S, H, D, cache.shape[3], _stream(qkv)), "kv_cache_store")
 
 
 # ----------------------------------------------------------------------------

@@ -25,9 +25,14 @@ against the composite that PHA_DECODE_ATTN=0 keeps.
     scrambled table against re-ordering the live part of every cache row with torch and then the
     per-row kernel: the design the table replaces.
 
+(e) with --q8: the int8-cache form (csrc/kernels/decode_attn_q8.hip, ``cache_scales``) against the 16-bit
+    kernel at B = 8, H = 16, max_seq = 2048, D in {128, 64} and ts in {127, 2047}, both arms one captured
+    graph over the 24 caches, alternating in one process. Bytes are what each form must read: rows [0, ts]
+    of K and V, 2 D per row in bf16, D + 4 in int8.
+
 Prints markdown tables. Usage: python tools/bench_decode_attn.py [--rounds 7] [--iters 960] [--skip-model]
                                                                  [--rows [--parent-lib NAME] [--skip-attention]]
-                                                                 [--beam]
+                                                                 [--beam] [--q8]
 """
 import argparse
 import ctypes
@@ -272,6 +277,44 @@ def bench_beam(rounds, iters, K=4):
     print()
 
 
+def bench_q8(rounds, iters):
+    reps = max(4, iters // LAYERS)
+    print(f"### (e) int8 KV cache: B={B} H={H} max_seq={MAX_SEQ}, qkv bf16, graph replay over {LAYERS} caches, "
+          f"us per call, median of {rounds} rounds x {reps} replays (min - max)\n")
+    print("| D | ts | 16-bit cache | int8 cache | int8 / 16-bit time | bytes 16-bit | bytes int8 | bytes ratio | "
+          "16-bit TB/s | int8 TB/s |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+
+    def us(t):
+        return f"{t[0] * 1e3 / LAYERS:.2f} ({t[1] * 1e3 / LAYERS:.2f} - {t[2] * 1e3 / LAYERS:.2f})"
+
+    for d in (128, 64):
+        g = torch.Generator(device="cuda").manual_seed(0)
+        qkv = torch.randn(B, 3, H, d, device="cuda", generator=g).bfloat16()
+        qb = (torch.randn(3, H, d, device="cuda", generator=g) * 0.1).bfloat16()
+        c16 = [torch.randn(2, B, H, MAX_SEQ, d, device="cuda", generator=g).bfloat16() for _ in range(LAYERS)]
+        c8, sc = zip(*(hip.kv_cache_quantize(c) for c in c16))
+        for ts in (127, 2047):
+            one = torch.tensor([ts], dtype=torch.int32, device="cuda")
+            fns = [lambda i: hip.decode_attention(qkv, qb, c16[i % LAYERS], one),
+                   lambda i: hip.decode_attention(qkv, qb, c8[i % LAYERS], one, cache_scales=sc[i % LAYERS])]
+            graphs = []
+            for fn in fns:
+                fn(0)
+                torch.cuda.synchronize()
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr):
+                    for i in range(LAYERS):
+                        fn(i)
+                graphs.append(gr)
+            r16, r8 = alternate([lambda _, gr=gr: gr.replay() for gr in graphs], reps, rounds)
+            b16, b8 = 2 * B * H * (ts + 1) * d * 2, 2 * B * H * (ts + 1) * (d + 4)
+            print(f"| {d} | {ts} | {us(r16)} | {us(r8)} | {r8[0] / r16[0]:.2f} | {b16 / 1e6:.1f} MB | {b8 / 1e6:.1f} MB | "
+                  f"{b8 / b16:.2f} | {b16 / (r16[0] / LAYERS * 1e-3) / 1e12:.2f} | {b8 / (r8[0] / LAYERS * 1e-3) / 1e12:.2f} |")
+            del graphs
+    print()
+
+
 def bench_model(rounds, iters):
     E, DFF, ts = H * D, 4 * H * D, 1023
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -328,6 +371,7 @@ def main():
     ap.add_argument("--skip-attention", action="store_true")
     ap.add_argument("--rows", action="store_true", help="part (c): per-row time steps")
     ap.add_argument("--beam", action="store_true", help="part (d): the beam-indirect form")
+    ap.add_argument("--q8", action="store_true", help="part (e): the int8-cache form against the 16-bit kernel")
     ap.add_argument("--parent-lib", default=None,
                     help="file name under paddle_hackathon_amd/_C/ of a library built from the parent commit's "
                          "decode_attn.hip, for the scalar arm of part (c)")
@@ -342,6 +386,8 @@ def main():
             bench_rows(a.rounds, a.iters, a.parent_lib)
         if a.beam:
             bench_beam(a.rounds, a.iters)
+        if a.q8:
+            bench_q8(a.rounds, a.iters)
     if not a.skip_model:
         bench_model(a.rounds, max(8, a.iters // LAYERS))
 

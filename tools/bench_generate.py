@@ -207,6 +207,43 @@ def bench_generate_w8(rounds, B=8, prompt=128, new=128):
           f"{100 * agree:.1f} % of the int8 tokens equal the bf16 ones (random weights)\n")
 
 
+def bench_generate_kv8(rounds, B=8, prompt=1920, new=128):
+    """--kv8: cache_dtype="int8" against the 16-bit cache at a long cache, with both weight modes, graph replay"""
+    import paddle_hackathon_amd as paddle
+    from paddle_hackathon_amd.models import GPTForPretraining, GPTGenerator, gpt_config
+    paddle.set_device("gpu:0")
+    paddle.seed(0)
+    model = paddle.amp.decorate(GPTForPretraining(gpt_config("gpt3-1.3b")), level="O2", dtype="bfloat16")
+    model.eval()
+    ids = torch.randint(0, V, (B, prompt), device="cuda", generator=torch.Generator(device="cuda").manual_seed(2))
+    gen = GPTGenerator(model)
+
+    def arm(weights, cache):
+        def fn():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out, _ = gen.generate(ids, new, use_graph=True, weight_only=weights, cache_dtype=cache)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, out._t
+        return fn
+
+    arms = [("bf16 weights, bf16 cache", arm(None, None)), ("bf16 weights, int8 cache", arm(None, "int8")),
+            ("int8 weights, bf16 cache", arm("int8", None)), ("int8 weights, int8 cache", arm("int8", "int8"))]
+    outs = [fn()[1] for _, fn in arms]   # warm-up: quantises the weights, captures the graphs
+    samples = [[] for _ in arms]
+    for _ in range(rounds):
+        for s, (_, fn) in zip(samples, arms):
+            s.append(fn()[0])
+    print(f"### (--kv8) generate, GPT-3 1.3B bf16, B = {B}, prompt {prompt}, {new} new tokens, greedy, graph replay, "
+          f"whole call (prefill included), median of {rounds} rounds (min - max)\n")
+    print("| path | ms per call | tokens equal to the bf16-cache arm |")
+    print("|---|---|---|")
+    for i, ((label, _), s) in enumerate(zip(arms, samples)):
+        med, lo, hi = statistics.median(s), min(s), max(s)
+        print(f"| {label} | {med:.1f} ({lo:.1f} - {hi:.1f}) | {100 * (outs[i] == outs[i & 2]).float().mean().item():.1f} % |")
+    print()
+
+
 def bench_ragged(rounds, B=8, prompt=128, new=128):
     import paddle_hackathon_amd as paddle
     from paddle_hackathon_amd.models import GPTForPretraining, GPTGenerator, gpt_config
@@ -325,6 +362,7 @@ def main():
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--ragged", action="store_true", help="part (d): prompts of different lengths")
     ap.add_argument("--beams", type=int, default=0, help="parts (e) and (f): beam search with this many beams")
+    ap.add_argument("--kv8", action="store_true", help="cache_dtype=\"int8\" against the 16-bit cache at a long cache")
     ap.add_argument("--w8", action="store_true", help="part (c): weight_only=\"int8\" against the bf16 weights")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -337,6 +375,8 @@ def main():
             bench_lm_head(a.rounds, a.iters)
         if not a.skip_model:
             (bench_generate_w8 if a.w8 else bench_generate)(a.rounds)
+        if a.kv8:
+            bench_generate_kv8(a.rounds)
         if a.ragged:
             bench_ragged(a.rounds)
         if a.beams:
