@@ -8,6 +8,7 @@ import numpy as np
 import torch
 import torch.nn.functional as TF
 
+from ... import ops as _ops
 from ...nn import functional as F
 from ._common import T, W, dev, to_padded, register
 
@@ -115,8 +116,7 @@ def warpctc(input, label, blank=0, norm_by_times=False, input_length=None, label
         xl = T(input_length).reshape(-1).long()
         y = T(label).reshape(T(label).shape[0], -1)
         yl = T(label_length).reshape(-1).long()
-    lp = torch.log_softmax(x.float(), -1)
-    loss = TF.ctc_loss(lp, y.long(), xl, yl, blank=blank, reduction="none", zero_infinity=False)
+    loss = _ops.ctc_loss(x, y.long(), xl, yl, blank, zero_infinity=False)
     if norm_by_times:
         loss = loss / xl.to(loss.dtype)
     _ = fcore

@@ -123,8 +123,7 @@ def binary_cross_entropy_with_logits(logit, label, weight=None, reduction="mean"
 
 
 def ctc_loss(log_probs, labels, input_lengths, label_lengths, blank=0, reduction="mean", norm_by_times=False):
-    lp = TF.log_softmax(log_probs._t.float(), -1)
-    loss = TF.ctc_loss(lp, labels._t, input_lengths._t, label_lengths._t, blank, reduction="none", zero_infinity=True)
+    loss = _ops.ctc_loss(log_probs._t, labels._t, input_lengths._t, label_lengths._t, blank, zero_infinity=True)
     if reduction == "mean":
         return _w((loss / label_lengths._t.clamp_min(1).float()).mean())
     return _w(_reduce(loss, reduction))

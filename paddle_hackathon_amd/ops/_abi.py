@@ -41,6 +41,11 @@ SIGNATURES = {
     "pha_embedding_bwd": (I, [I, P, P, P, LG, I, LG, LG, P, I, P]),
     "pha_embedding_fwd": (I, [P, P, P, LG, I, LG, P]),
     "pha_seed_bump": (I, [P, P, P]),
+    # ctc.hip
+    "pha_ctc_max_label": (I, []),
+    "pha_ctc_max_v": (I, []),
+    "pha_ctc_fwd": (I, [I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "pha_ctc_bwd": (I, [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     # decode_attn.hip
     "pha_decode_attn_chunk": (I, []),
     "pha_decode_attn": (I, [I, P, P, P, P, LG, LG, F, I, P, P, P, I, I, I, I, P]),

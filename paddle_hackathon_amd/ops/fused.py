@@ -4,6 +4,7 @@ Reference parity (what each op replaces in the reference):
   * layer_norm       — phi/kernels/gpu/layer_norm_kernel.cu, layer_norm_grad_kernel.cu
   * softmax          — phi/kernels/gpu/softmax_kernel.cu (gpudnn/softmax_gpudnn.h)
   * softmax_cross_entropy — phi/kernels/gpu/cross_entropy_kernel.cu (softmax_with_cross_entropy)
+  * ctc_loss         — phi/kernels/gpu/warpctc_kernel.cu, warpctc_grad_kernel.cu
   * gelu / bias_gelu — phi/kernels/gpu/gelu_kernel.cu, operators/fused/fused_dropout_act_bias.h
   * fused_adam_      — phi/kernels/gpu/adam_kernel.cu (+ multi_tensor_adam in fluid/operators/optimizers)
   * fused_momentum_  — phi/kernels/gpu/merged_momentum_kernel.cu
@@ -265,6 +266,44 @@ def softmax_cross_entropy(logits, labels, ignore_index=-100):
         l2 = l2.float() if l2.dtype in (torch.float16, torch.bfloat16) else l2
         loss = TF.cross_entropy(l2, lab.long(), reduction="none", ignore_index=ignore_index)
     return loss.reshape(shp)
+
+
+# ----------------------------------------------------------------------------
+# CTC loss
+# ----------------------------------------------------------------------------
+class _CTCLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, input_lengths, label_lengths, blank, zero_infinity):
+        loss, saved = _hip.ctc_fwd(logits, labels, input_lengths, label_lengths, blank, zero_infinity)
+        ctx.save_for_backward(logits, *saved)
+        ctx.blank, ctx.zero_infinity = blank, zero_infinity
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        logits, *saved = ctx.saved_tensors
+        gx = _hip.ctc_bwd(gloss.contiguous().float(), logits, saved, ctx.blank, ctx.zero_infinity)
+        return gx, None, None, None, None, None
+
+
+def ctc_loss(logits, labels, input_lengths, label_lengths, blank=0, zero_infinity=False):
+    """Per-sample CTC loss (fp32 [B]) from unnormalised logits [T, B, V]; ``zero_infinity`` gives an
+    infeasible sample loss 0 and gradient 0 instead of inf.
+
+    On a GPU the loss and its gradient run on the kernels of csrc/kernels/ctc.hip, which fold the
+    softmax in and never form the [T, B, V] log-probabilities (``hip.ctc_loss_supported`` says what
+    they take: padded labels [B, Lmax <= 511], V <= 32,768, lengths on the device). The CPU,
+    DTensors and whatever the kernels decline (on a GPU recorded as a ``ctc_loss`` fallback) run
+    log_softmax + torch's ctc_loss in fp32. PHA_CTC_KERNEL=0 selects that composite."""
+    if logits.is_cuda and os.environ.get("PHA_CTC_KERNEL", "1") != "0" and _use_hip(logits):
+        xc = logits.contiguous()   # a [B, T, V] head output transposed to [T, B, V]: one copy, its gradient flows back
+        why = _hip.ctc_loss_why_not(xc, labels, input_lengths, label_lengths, blank)
+        if why is None:
+            return _CTCLoss.apply(xc, labels, input_lengths, label_lengths, int(blank), bool(zero_infinity))
+        from . import fallback
+        fallback.note("ctc_loss", why + " -> torch composite")
+    lp = TF.log_softmax(logits.float(), -1)
+    return TF.ctc_loss(lp, labels, input_lengths, label_lengths, blank, reduction="none", zero_infinity=zero_infinity)
 
 
 # ----------------------------------------------------------------------------

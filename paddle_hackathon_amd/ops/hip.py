@@ -259,6 +259,90 @@ def softmax_ce_bwd(gloss, logits, labels, stats, ignore_index):
     return dx
 
 
+# ----------------------------------------------------------------------------
+# CTC loss (csrc/kernels/ctc.hip)
+# ----------------------------------------------------------------------------
+def _ctc_limits():
+    if _lib.lib is None:
+        return 0, 0
+    return _lib.lib.pha_ctc_max_label(), _lib.lib.pha_ctc_max_v()
+
+
+CTC_MAX_LABEL, CTC_MAX_V = _ctc_limits()   # the kernels' label-length and vocabulary limits (0: library not built)
+
+
+def ctc_loss_why_not(logits, labels, input_lengths, label_lengths, blank=0):
+    """the reason the CTC kernels would reject these arguments, or None when they take them"""
+    if _lib.lib is None:
+        return "kernel library not loaded"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3 or not logits.is_cuda:
+        return "logits are not a 3-D GPU tensor [T, B, V]"
+    T, B, V = logits.shape
+    if logits.dtype not in _DT:
+        return f"logits are {logits.dtype}; bfloat16, float16 or float32 expected"
+    if T < 1 or B < 1 or V < 1:
+        return f"empty logits {tuple(logits.shape)}"
+    if V > CTC_MAX_V:
+        return f"V={V} is above the kernel's {CTC_MAX_V} (one fp32 accumulator per class in LDS)"
+    if not logits.is_contiguous() or logits.data_ptr() % 16:
+        return "logits are not contiguous and 16-byte aligned"
+    ints = (torch.int32, torch.int64)
+    for name, v in (("labels", labels), ("input_lengths", input_lengths), ("label_lengths", label_lengths)):
+        if not isinstance(v, torch.Tensor) or v.device != logits.device or v.dtype not in ints:
+            return f"{name} is not an integer tensor on the logits' device"
+    if labels.dim() != 2 or labels.shape[0] != B:
+        return "labels are not padded [B, Lmax] (the concatenated 1-D form needs the lengths on the host)"
+    if labels.shape[1] > CTC_MAX_LABEL:
+        return f"Lmax={labels.shape[1]} is above the kernel's {CTC_MAX_LABEL} (2 Lmax + 1 positions per LDS row)"
+    if input_lengths.numel() != B or label_lengths.numel() != B:
+        return "input_lengths / label_lengths do not have one entry per sample"
+    if not 0 <= int(blank) < V:
+        return f"blank={blank} is outside [0, {V})"
+    return None
+
+
+def ctc_loss_supported(logits, labels, input_lengths, label_lengths, blank=0):
+    """what the CTC kernels take: contiguous bf16 / fp16 / fp32 logits [T, B, V] on a GPU with V <= CTC_MAX_V
+    (32,768), padded integer labels [B, Lmax] with Lmax <= CTC_MAX_LABEL (511), integer lengths [B], all on
+    the logits' device, and 0 <= blank < V"""
+    return ctc_loss_why_not(logits, labels, input_lengths, label_lengths, blank) is None
+
+
+def ctc_fwd(logits, labels, input_lengths, label_lengths, blank, zero_infinity):
+    """(loss [B], saved) in fp32 from logits [T, B, V]; ``saved`` = (labels, lengths, stats [2, T, B], workspace
+    [2, B, T, 2 Lmax + 1], nll [B]) is what ctc_bwd reads. Lengths and labels never reach the host."""
+    why = ctc_loss_why_not(logits, labels, input_lengths, label_lengths, blank)
+    if why is not None:
+        raise ValueError(f"ctc_fwd: {why}")
+    T, B, V = logits.shape
+    Lmax = labels.shape[1]
+    dev = logits.device
+    labels = labels.to(torch.int64).contiguous()
+    il = input_lengths.reshape(-1).to(torch.int64).contiguous()
+    ll = label_lengths.reshape(-1).to(torch.int64).contiguous()
+    stats = torch.empty((2, T, B), dtype=torch.float32, device=dev)
+    ws = torch.empty((2, B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev)
+    nll = torch.empty(B, dtype=torch.float32, device=dev)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    _check(_L().pha_ctc_fwd(_DT[logits.dtype], _ptr(logits), _ptr(labels), _ptr(il), _ptr(ll), _ptr(stats), _ptr(ws),
+                            _ptr(nll), _ptr(loss), T, B, V, Lmax, int(blank), int(bool(zero_infinity)), _stream(logits)),
+           "ctc_fwd")
+    return loss, (labels, il, ll, stats, ws, nll)
+
+
+def ctc_bwd(gloss, logits, saved, blank, zero_infinity):
+    """d loss / d logits (the logits' dtype) times gloss [B] (fp32); ``saved`` from ctc_fwd"""
+    labels, il, ll, stats, ws, nll = saved
+    T, B, V = logits.shape
+    assert gloss.dtype == torch.float32 and gloss.numel() == B and gloss.is_contiguous()
+    assert ws.shape == (2, B, T, 2 * labels.shape[1] + 1) and stats.shape == (2, T, B)
+    dx = torch.empty_like(logits)
+    _check(_L().pha_ctc_bwd(_DT[logits.dtype], _ptr(logits), _ptr(labels), _ptr(il), _ptr(ll), _ptr(stats), _ptr(ws),
+                            _ptr(nll), _ptr(gloss), _ptr(dx), T, B, V, labels.shape[1], int(blank),
+                            int(bool(zero_infinity)), _stream(logits)), "ctc_bwd")
+    return dx
+
+
 def bias_gelu_fwd(x, b, approximate):
     n = x.numel()
     H = x.shape[-1]
